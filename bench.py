@@ -97,7 +97,11 @@ def parse():
                     help="BASELINE.json configs[i]; 2-4 = the 300 GB standard-geometry database in 8 shards, sharded mode")
     ap.add_argument("--db-shards", type=int, default=0,
                     help="sharded mode: minimizer-range shards the database is cut into (rank r holds shard r; default: one per rank)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     a = ap.parse_args()
+    if a.dump_outputs and a.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
     a.mode_given = a.mode is not None
     a.mode = a.mode or "replicas"
     a.preset = None
@@ -479,6 +483,57 @@ def host_legs(a, db, ctx, batch, read_len, calls_gpu, taxa_gpu, k, algo_bytes0=N
     return out
 
 
+# --dump-outputs: bounds of what is written (float64 but the registers; under 64 MB in all for any batch)
+DUMP_SEED = 20261015
+DUMP_MAX_READS = 1 << 20       # calls: a fixed sample of this many of the step's reads
+DUMP_MAX_CODES = 2 << 20       # per-k-mer codes: of the first reads of that sample, this many at most
+DUMP_MAX_REGISTERS = 4 << 20   # HLL registers: every slot at a fixed sample of register indices, this many at most
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, k, d_calls, d_off, d_len, read_lo, read_hi, counts, d_taxa=None, runs=None):
+    """--dump-outputs: what the timed path's last step handed its caller, as DIR/<name>.npy, so that two builds can be
+    compared output for output (the inputs of a run are seeded: the same arguments give the same reads and database).
+      read_index   the reads sampled (DUMP_SEED, at most DUMP_MAX_READS of [read_lo, read_hi)), ascending
+      calls        their calls (taxids)
+      codes        the per-k-mer codes of the sample's first reads, read after read (the per-position array, or the
+                   kernel's runs expanded: --output runs), at most DUMP_MAX_CODES
+      slot_taxid, n_kmers, node_taxid, n_reads   the per-taxon state after the step (ku_counts_export)
+      registers    its HLL registers, every slot at a seeded sample of register indices (float32)
+    runs = (d_runs, d_run_off, d_run_cnt) when the step wrote runs instead of d_taxa."""
+    from krakenuniq_amd import synth_torch
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    n = read_hi - read_lo
+    sel = np.sort(rng.choice(n, size=min(n, DUMP_MAX_READS), replace=False)).astype(np.int64) + read_lo
+    dev = d_calls.device
+    sel_t = torch.from_numpy(sel).to(dev)
+    out = {"read_index": sel.astype(np.float64),
+           "calls": d_calls[sel_t].cpu().numpy().view(np.uint32).astype(np.float64)}
+    nk = torch.clamp(d_len[sel_t].to(torch.int64) - (k - 1), min=0)
+    head = max(1, int(torch.searchsorted(torch.cumsum(nk, 0), DUMP_MAX_CODES, right=True).item())) if len(sel) else 0
+    t_sel, t_nk = sel_t[:head], nk[:head]
+    if runs is not None:
+        d_runs, d_roff, d_rcnt = runs
+        codes = synth_torch.expand_runs(d_runs, d_roff[t_sel], d_rcnt[t_sel], t_nk)
+    else:
+        total = int(t_nk.sum().item())
+        first = torch.cumsum(t_nk, 0) - t_nk
+        read_of = torch.repeat_interleave(torch.arange(head, device=dev), t_nk)
+        pos = d_off[t_sel].to(torch.int64)[read_of] + (torch.arange(total, device=dev) - first[read_of])
+        codes = d_taxa[pos]
+    out["codes"] = codes[:DUMP_MAX_CODES].cpu().numpy().view(np.uint32).astype(np.float64)
+    for key in ("slot_taxid", "n_kmers", "node_taxid", "n_reads"):
+        out[key] = counts[key].astype(np.float64)
+    regs = counts["registers"]
+    n_cols = max(1, min(regs.shape[1], DUMP_MAX_REGISTERS // max(1, regs.shape[0])))
+    cols = np.sort(rng.choice(regs.shape[1], size=n_cols, replace=False))
+    out["registers"] = regs[:, cols].astype(np.float32)
+    assert sum(v.nbytes for v in out.values()) <= DUMP_MAX_BYTES, "--dump-outputs: more than 64 MB"
+    for key, v in out.items():
+        np.save(os.path.join(path, key + ".npy"), v)
+
+
 def windowed_shapes(a, db, ctx, k, dev, stream, rev):
     """Extras of the default line: the fused kernel's WINDOWED instance (reads beyond 192 k-mers: mate pairs 2 x 150 + N, 10 kbp
     reads) on the same database -- the batches `--paired --reads 5000000` / `--read-len 10000 --reads 100000` time, one warm-up
@@ -538,7 +593,7 @@ def shard_bounds(synth_torch, dev, a, k, n_shards):
     return synth_torch.quantile_bin_bounds(bins, 4 ** a.nt, n_shards)
 
 
-def sharded_run(a, capi, synth_torch, dev, rank, local_rank, ws, uid, k, steps, warmup, stream):
+def sharded_run(a, capi, synth_torch, dev, rank, local_rank, ws, uid, k, steps, warmup, stream, dump=None):
     """the sharded step through ku_mgpu_step_device; returns a dict: elapsed seconds over `steps`, the group, the shard,
     whether every read was resolved exactly once, and the rank's own kernel measurements"""
     n_shards = max(a.db_shards or ws, ws)
@@ -607,6 +662,9 @@ def sharded_run(a, capi, synth_torch, dev, rank, local_rank, ws, uid, k, steps, 
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else torch.device("cpu"))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump and rank == 0:  # rank 0's slice of the last step (it holds the batches)
+        b = batches[(steps - 1) % len(batches)]
+        dump_outputs(dump, k, d_calls, b[1], b[2], rb[0], rb[1], mg.ctx(0).counts(), d_taxa=d_taxa)
     # every read was resolved exactly once over the whole world
     total_reads = int(mg.ctx(0).counts()["n_reads"].sum())
     ctx = mg.ctx(0)
@@ -849,7 +907,7 @@ def main():
         t_build = time.time()
         run_state["doing"] = "the sharded run (shard synthesis, probe table, routed steps)"
         pf = preflight(a, rank, ws, local_rank, dev, "sharded", a.species, a.genome_len, a.nt, max(a.db_shards or ws, ws), a.reads, t_start) if ws > 1 or a.config != 1 else None
-        sr = sharded_run(a, capi, synth_torch, dev, rank, local_rank, ws, uid, k, a.steps, a.warmup, stream)
+        sr = sharded_run(a, capi, synth_torch, dev, rank, local_rank, ws, uid, k, a.steps, a.warmup, stream, dump=a.dump_outputs)
         elapsed, mg, db, L = sr["elapsed"], sr["mg"], sr["db"], sr["read_len"]
         value = a.reads * a.steps / elapsed / 1e6
         ctx = mg.ctx(0)
@@ -973,6 +1031,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kernel_ms = float(np.mean([s.elapsed_time(e) for s, e in ev])) if a.steps else 0.0
+    if a.dump_outputs and rank == 0:  # before the legs below write into the same buffers
+        b = batches[(a.steps - 1) % nb_batches]
+        dump_outputs(a.dump_outputs, k, d_calls, b[1], b[2], 0, a.reads, ctx.counts(), d_taxa=None if runs_out else d_taxa,
+                     runs=(d_runs, d_roff, d_rcnt) if runs_out else None)
     state_ok = None
     if mg:  # the reads of the last (possibly partial) rotation of every rank, summed over the world
         last_rot = a.steps - ((a.steps - 1) // nb_batches) * nb_batches
@@ -1159,7 +1221,8 @@ def main():
             s_warm = a.warmup if headline else 1
             pf_sh = preflight(a2, rank, ws, local_rank, dev, "sharded", a2.species, a2.genome_len, a2.nt, max(a2.db_shards or ws, ws), a2.reads, t_start)
             pf_sh["leg_limit_s"] = round(leg_limit)
-            sr = sharded_run(a2, capi, synth_torch, dev, rank, local_rank, ws, fresh_uid(), k, s_steps, s_warm, stream)
+            sr = sharded_run(a2, capi, synth_torch, dev, rank, local_rank, ws, fresh_uid(), k, s_steps, s_warm, stream,
+                             dump=a.dump_outputs if headline else None)
             el = sr["elapsed"]
             result["sharded"] = {"value": round(a2.reads * s_steps / el / 1e6, 3), "unit": "Mreads/s", "scaling": "strong",
                                  "steps": s_steps, "warmup": s_warm, "ms_per_step": round(el / s_steps * 1e3, 3), "db_pairs_per_gpu": sr["db"].n_pairs,

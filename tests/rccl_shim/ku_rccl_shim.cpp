@@ -10,9 +10,12 @@
 //
 // Round 5: the operations are ASYNCHRONOUS, as RCCL's are.  A call (or a group) only ENQUEUES on its stream and returns:
 //   copies of the send buffers into page-locked staging memory (stream order: they see what the stream produced before),
-//   a host function (hipLaunchHostFunc) that writes the messages, then waits for the peers' and folds reductions -- the
-//   stream stands still meanwhile, as it does inside a collective --, the copies of the staged receive data into place,
-//   and a second host function that hands the staging memory back.
+//   a one-thread kernel that holds the stream until a page-locked flag is set -- the stream stands still meanwhile, as it
+//   does inside a collective --, and the copies of the staged receive data into place.  A host thread of the exchange's
+//   own waits for the staging copies, writes the messages, waits for the peers' and folds reductions, then sets the flag.
+//   (Not a host function on the stream: the runtime runs those one after the other on one thread per process, so an
+//   exchange that waits for a peer would hold up the exchanges of every other stream -- two ranks whose streams reach
+//   their exchanges in different orders then wait for each other for ever, and a lag meant for one stream delays all.)
 // So a buffer the driver reuses too early, or a stream that does not wait for the one that produced the data, shows as wrong
 // data -- the synchronous stand-in of round 4 (KU_SHIM_SYNC=1 brings it back: every operation synchronised its stream and
 // blocked the caller) hid exactly that.  KU_SHIM_JITTER_US=N delays every exchange by a random time below N microseconds, a
@@ -207,8 +210,23 @@ struct Group {
   std::vector<Op> ops;
   std::vector<void *> h_send, h_recv;  // page-locked staging per operation (nullptr: none)
   std::vector<size_t> recv_bytes;
-  std::atomic<int> done{0};
+  hipEvent_t staged = nullptr, finished = nullptr;  // behind the staging copies / behind the copies into place
+  int *flag = nullptr;                              // page-locked: set by the exchange thread, watched by wait_for_host
+  std::thread worker;
+  std::atomic<bool> worker_done{false};
 };
+// holds the stream until the exchange thread sets *flag (bounded: a thread that never comes cannot hold the device)
+__global__ void wait_for_host(const int *flag, unsigned long long max_ticks) {
+  const unsigned long long t0 = wall_clock64();
+  while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) == 0 && wall_clock64() - t0 < max_ticks)
+    __builtin_amdgcn_s_sleep(64);
+}
+unsigned long long wait_ticks() {  // the host's own timeout and a minute more, in wall-clock ticks of the device
+  int dev = 0, khz = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0)
+    khz = 100000;
+  return (unsigned long long)((timeout_s() + 60.0) * 1e3 * khz);
+}
 // KU_SHIM_LAG_OTHER_STREAMS_US=N: every exchange on a stream other than the communicator's first one finishes N microseconds
 // late -- deterministically: a caller that does not wait for its second stream reads what is not there yet
 void lag_other_streams(const Group *g) {
@@ -248,11 +266,10 @@ void take_numbers(Op &o) {
       break;
   }
 }
-// runs on a runtime thread while the stream stands still: no HIP calls in here
-void exchange_host(void *arg) {
-  Group *g = (Group *)arg;
+// the exchange's own thread, while the stream stands still in wait_for_host
+void exchange_host(Group *g) {
   ncclComm *c = g->comm;
-  bool ok = true;
+  bool ok = hipEventSynchronize(g->staged) == hipSuccess;
   jitter(c);
   for (size_t i = 0; i < g->ops.size() && ok; ++i) {  // every send of the group is out ...
     const Op &o = g->ops[i];
@@ -297,18 +314,27 @@ void exchange_host(void *arg) {
     c->failed = true;
     fprintf(stderr, "[ku_rccl_shim] rank %d: an exchange failed (a peer did not deliver, or a message of the wrong size)\n", c->rank);
   }
+  __atomic_store_n(g->flag, 1, __ATOMIC_RELEASE);
+  g->worker_done = true;
 }
-void release_host(void *arg) { ((Group *)arg)->done = 1; }
-void collect(ncclComm *c, bool all) {  // staging memory of the exchanges that are through (caller's thread: HIP calls allowed)
+// staging memory of the exchanges that are through: their thread has ended and their stream is past the copies into place
+// (`all`: every one, the device synchronised before -- also those whose enqueueing failed half-way)
+void collect(ncclComm *c, bool all) {
   std::vector<Group *> keep, gone;
   {
     std::lock_guard<std::mutex> l(c->mu);
-    for (Group *g : c->groups) (g->done.load() || all ? gone : keep).push_back(g);
+    for (Group *g : c->groups) {
+      const bool through = g->worker.joinable() && g->worker_done.load() && hipEventQuery(g->finished) == hipSuccess;
+      (through || all ? gone : keep).push_back(g);
+    }
     c->groups.swap(keep);
   }
   for (Group *g : gone) {
+    if (g->worker.joinable()) g->worker.join();
     for (void *p : g->h_send) if (p) (void)hipHostFree(p);
     for (void *p : g->h_recv) if (p) (void)hipHostFree(p);
+    if (g->flag) (void)hipHostFree(g->flag);
+    for (hipEvent_t e : {g->staged, g->finished}) if (e) (void)hipEventDestroy(e);
     delete g;
   }
 }
@@ -347,10 +373,23 @@ ncclResult_t enqueue_group(std::vector<Op> &ops) {
     if (ok && rb) ok = hipHostMalloc(&g->h_recv[i], rb, hipHostMallocDefault) == hipSuccess;
     g->recv_bytes[i] = rb;
   }
-  if (ok) ok = hipLaunchHostFunc(s, exchange_host, g) == hipSuccess;
+  if (ok) ok = hipHostMalloc((void **)&g->flag, sizeof(int), hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
+  if (ok) *g->flag = 0;
+  for (hipEvent_t *e : {&g->staged, &g->finished})
+    if (ok) ok = hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+  if (ok) ok = hipEventRecord(g->staged, s) == hipSuccess;
+  int *d_flag = nullptr;
+  if (ok) ok = hipHostGetDevicePointer((void **)&d_flag, g->flag, 0) == hipSuccess;
+  if (ok) {
+    static const unsigned long long ticks = wait_ticks();
+    hipLaunchKernelGGL(wait_for_host, dim3(1), dim3(1), 0, s, d_flag, ticks);
+    ok = hipGetLastError() == hipSuccess;
+  }
   for (size_t i = 0; i < n && ok; ++i)
     if (g->recv_bytes[i] && g->ops[i].recv) ok = hipMemcpyAsync(g->ops[i].recv, g->h_recv[i], g->recv_bytes[i], hipMemcpyHostToDevice, s) == hipSuccess;
-  if (ok) ok = hipLaunchHostFunc(s, release_host, g) == hipSuccess;
+  if (ok) ok = hipEventRecord(g->finished, s) == hipSuccess;
+  if (ok) g->worker = std::thread(exchange_host, g);
+  else if (g->flag) __atomic_store_n(g->flag, 1, __ATOMIC_RELEASE);  // (a wait kernel already queued lets the stream go)
   {
     std::lock_guard<std::mutex> l(c->mu);
     c->groups.push_back(g);

@@ -3,7 +3,10 @@
 KU_RCCL_LIB pointing at libku_rccl_shim.so): the driver's RCCL code paths -- ncclCommInitRank, grouped send / receive
 all-to-alls, the scatter of the read slices, the all-gathers of values and routing counts, the all-reduce of the state --
 run between real peers.  Every rank checks its own slice against one context that holds the whole database.
-    worker.py <rank> <world> <mode: route|slots|reduce|replicas> <scratch dir>"""
+    worker.py <rank> <world> <mode: route|slots|reduce|replicas> <scratch dir>
+KU_WORKER_CALLER_STREAM=1: the sharded steps run on a stream of the worker's own, and their results are read on that stream
+only (the null stream of the runtime may wait for every stream of the device, which would hide a step that returns before
+its work is joined into the caller's stream)."""
 import os
 import sys
 import time
@@ -83,6 +86,7 @@ else:
     mg.ctx(0).adopt_db(sh.pairs.data_ptr(), sh.n_pairs, sh.offsets.data_ptr(), K, NT, 2, bounds[rank], bounds[rank + 1])
     mg.set_taxonomy(ctax)
     assert mg.uses_routing() == (mode == "route")
+    cs = torch.cuda.Stream(device=dev) if os.environ.get("KU_WORKER_CALLER_STREAM") == "1" else None
     rb = [N * r // W for r in range(W + 1)]
     pb = [x * stride for x in rb]
     buf = {"seqs": torch.zeros(nb + 16, dtype=torch.uint8, device=dev), "off": torch.zeros(N, dtype=torch.int64, device=dev),
@@ -95,11 +99,16 @@ else:
             buf["len"][:] = lens
         torch.cuda.synchronize()
         mg.step_device([{"d_seqs": buf["seqs"].data_ptr(), "d_seq_off": buf["off"].data_ptr(), "d_seq_len": buf["len"].data_ptr(),
-                         "d_calls": buf["calls"].data_ptr(), "d_taxa": buf["taxa"].data_ptr()}], nb, N, rb, pb, max_read_len=L)
-        mg.ctx(0).synchronize()
+                         "d_calls": buf["calls"].data_ptr(), "d_taxa": buf["taxa"].data_ptr(),
+                         "stream": cs.cuda_stream if cs else None}], nb, N, rb, pb, max_read_len=L)
+        if cs:
+            cs.synchronize()
+        else:
+            mg.ctx(0).synchronize()
         lo, hi = rb[rank], rb[rank + 1]
-        assert torch.equal(buf["calls"][lo:hi], calls1[lo:hi]), "calls of the slice differ"
-        assert torch.equal(buf["taxa"][:nb].view(N, stride)[lo:hi, :nk], taxa1.view(N, stride)[lo:hi, :nk]), "per-k-mer codes of the slice differ"
+        with torch.cuda.stream(cs):
+            assert torch.equal(buf["calls"][lo:hi], calls1[lo:hi]), "calls of the slice differ"
+            assert torch.equal(buf["taxa"][:nb].view(N, stride)[lo:hi, :nk], taxa1.view(N, stride)[lo:hi, :nk]), "per-k-mer codes of the slice differ"
     mg.reduce_state()
     assert same_counts(mg.ctx(0).counts(), want_counts), "the reduced per-taxon state differs"
 mg.close()

@@ -46,3 +46,52 @@ def test_routed_traffic_of_the_profiled_and_of_the_full_world(tmp_path):
     t, note = b.routed_traffic(path, "000000000000", 15, 96000, 8, 8, 10_000_000, 150, 1.0)
     assert t is None and "refused" in note
     assert b.routed_traffic(str(tmp_path / "missing.json"), rev, 15, 96000, 8, 8, 10_000_000, 150, 1.0)[0] is None
+
+
+def test_dump_outputs_is_a_seeded_sample_of_what_the_step_returned(tmp_path):
+    """--dump-outputs on host tensors: the sampled calls and per-k-mer codes are the step's own, the per-position array and
+    the kernel's runs give the same files, and two dumps of one step are identical"""
+    import numpy as np
+    import torch
+    b = load_bench()
+    k, n, L = 31, 3000, 45
+    stride, nk = L + 1, L - k + 1
+    g = torch.Generator().manual_seed(3)
+    d_calls = torch.randint(0, 1 << 31, (n,), generator=g, dtype=torch.int64).to(torch.int32)
+    d_off = torch.arange(n, dtype=torch.int64) * stride
+    d_len = torch.full((n,), L, dtype=torch.int32)
+    per_kmer = torch.randint(-3, 3, (n, nk), generator=g, dtype=torch.int32).cumsum(1).div(4, rounding_mode="floor").to(torch.int32)  # runs of equal codes
+    d_taxa = torch.zeros(n * stride, dtype=torch.int32)
+    d_taxa.view(n, stride)[:, :nk] = per_kmer
+    runs, roff, rcnt = [], [], []
+    for r in per_kmer.tolist():
+        roff.append(len(runs))
+        for j, c in enumerate(r):
+            if j == 0 or c != r[j - 1]:
+                runs.append((c, j))
+        rcnt.append(len(runs) - roff[-1])
+    runs_t = (torch.tensor(runs, dtype=torch.int32), torch.tensor(roff, dtype=torch.int64), torch.tensor(rcnt, dtype=torch.int32))
+    rng = np.random.default_rng(5)
+    counts = {"slot_taxid": np.arange(7, dtype=np.uint32), "n_kmers": rng.integers(0, 1 << 40, 7).astype(np.uint64),
+              "registers": rng.integers(0, 40, (7, 4096)).astype(np.uint8), "node_taxid": np.arange(9, dtype=np.uint32),
+              "n_reads": rng.integers(0, 1000, 9).astype(np.uint64)}
+    dirs = [tmp_path / "a", tmp_path / "b", tmp_path / "c"]
+    b.dump_outputs(str(dirs[0]), k, d_calls, d_off, d_len, 0, n, counts, d_taxa=d_taxa)
+    b.dump_outputs(str(dirs[1]), k, d_calls, d_off, d_len, 0, n, counts, d_taxa=d_taxa)
+    b.dump_outputs(str(dirs[2]), k, d_calls, d_off, d_len, 0, n, counts, runs=runs_t)
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(f"{x}.npy" for x in ("read_index", "calls", "codes", "slot_taxid", "n_kmers", "node_taxid", "n_reads", "registers"))
+    total = 0
+    for name in names:
+        x = np.load(dirs[0] / name)
+        assert x.dtype in (np.float32, np.float64), name
+        total += x.nbytes
+        for d in dirs[1:]:
+            assert np.array_equal(x, np.load(d / name)), name
+    assert total <= 64 << 20
+    sel = np.load(dirs[0] / "read_index.npy").astype(np.int64)
+    assert len(sel) == n and (np.diff(sel) > 0).all()
+    assert np.array_equal(np.load(dirs[0] / "calls.npy"), d_calls.numpy()[sel].view(np.uint32).astype(np.float64))
+    assert np.array_equal(np.load(dirs[0] / "codes.npy"), per_kmer.numpy()[sel].reshape(-1).view(np.uint32).astype(np.float64))
+    assert np.array_equal(np.load(dirs[0] / "n_kmers.npy"), counts["n_kmers"].astype(np.float64))
+    assert np.load(dirs[0] / "registers.npy").shape == (7, 4096)

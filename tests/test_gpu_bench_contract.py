@@ -53,6 +53,25 @@ def test_other_shapes_run(shape):
     assert d["config"]["output"]["expanded_runs_equal_the_per_kmer_array"] is True
 
 
+def test_dump_outputs_of_the_last_step(tmp_path):
+    """--dump-outputs: the same arguments write the same arrays (float32 / float64, under 64 MB); the kernel's runs
+    (--output runs) give the calls and per-k-mer codes of the per-position array"""
+    import numpy as np
+    dirs = [tmp_path / "taxa", tmp_path / "again", tmp_path / "runs"]
+    for d, extra in zip(dirs, [(), (), ("--output", "runs")]):
+        assert run_bench("--cpu-sample", "0", "--no-extras", "--dump-outputs", str(d), *extra)["steps"] == 3
+    names = sorted(p.stem for p in dirs[0].iterdir())
+    assert {"calls", "codes", "read_index", "n_kmers", "registers"} <= set(names)
+    arrays = [{n: np.load(d / f"{n}.npy") for n in names} for d in dirs]
+    assert all(x.dtype in (np.float32, np.float64) for x in arrays[0].values())
+    assert sum(x.nbytes for x in arrays[0].values()) <= 64 << 20
+    assert (arrays[0]["calls"] != 0).any() and (arrays[0]["n_kmers"] > 0).any()
+    for n in names:
+        assert np.array_equal(arrays[0][n], arrays[1][n]), n
+    for n in ("read_index", "calls", "codes"):
+        assert np.array_equal(arrays[0][n], arrays[2][n]), n
+
+
 def run_bench_world(n, *extra):
     """`bench.py --gpus n` on a box with ONE GPU: every rank on cuda:0 (KU_BENCH_ONE_DEVICE), the C++ driver bound to the test
     stand-in for RCCL (tests/rccl_shim), which moves the ranks' messages between the processes"""

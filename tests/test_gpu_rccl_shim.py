@@ -77,7 +77,8 @@ def test_a_missing_stream_dependency_is_found():
     (KU_TEST_DROP_STREAM_JOIN): behind an asynchronous exchange that lags, the caller reads results that are not there yet --
     the step must FAIL.  (What the stand-in is for: the first run on several physical GPUs must not be the first time such a
     bug can show.)"""
-    env = {"KU_ROUTE_ROUND": "1500000", "KU_ROUTE_TWO_STREAMS": "1", "KU_SHIM_JITTER_US": "2000", "KU_SHIM_LAG_OTHER_STREAMS_US": "150000"}
+    env = {"KU_ROUTE_ROUND": "1500000", "KU_ROUTE_TWO_STREAMS": "1", "KU_SHIM_JITTER_US": "2000", "KU_SHIM_LAG_OTHER_STREAMS_US": "150000",
+           "KU_WORKER_CALLER_STREAM": "1"}  # (results read on the caller's stream alone: nothing else may join the streams)
     run_world(2, "route", env)  # with the join: fine, however the peers lag
     run_world(2, "route", dict(env, KU_TEST_DROP_STREAM_JOIN="1"), expect_failure=True)
 
