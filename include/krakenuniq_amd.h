@@ -111,6 +111,7 @@ uint32_t ku_tax_parent(const ku_tax *tax, uint32_t taxid);
  * n_reads) -- the device twin of the global `taxon_counts` map (classify.cpp:78). */
 typedef struct ku_ctx ku_ctx;
 int ku_ctx_create(int device, ku_ctx **out);
+/* waits for all of the context's work first -- batches still in flight included, whose copies go into caller memory */
 void ku_ctx_destroy(ku_ctx *ctx);
 
 /* Upload the shard [bin_lo, bin_hi) of a host DB.  Device twin of
@@ -283,9 +284,18 @@ int ku_fetch_runs(ku_ctx *ctx, ku_run *runs, uint64_t n_runs);
  * several batches in flight hide it.)  KU_ESTATE from _enqueue: KU_RLE_MAX_IN_FLIGHT batches are in flight already, or
  * the batch takes a path that cannot overlap (quick mode, several databases, sorted layout, a shard, exact counting, a
  * read beyond 65535 k-mers, an open work unit left by such a batch) while another is in flight: finish that one, then
- * enqueue again -- the batch is then classified inside _enqueue and _finish merely hands its totals over.  The entry
- * points that read or reset the run's state (reports, exports, ku_ctx_reset_counts, ku_sparse_close_unit,
- * ku_ctx_replace_calls, ku_classify_batch_rle itself) answer KU_ESTATE while batches are in flight. */
+ * enqueue again -- the batch is then classified inside _enqueue and _finish merely hands its totals over.
+ * While batches are in flight on a context, every entry point that takes it (or a group holding it) does one of three things
+ * (the table is tests/inflight_contract.py):
+ *   - KU_ESTATE, with no side effect: everything that reads, resets or merges the run's state (reports, exports, counts
+ *     exports -- exact ones included --, ku_ctx_reset_counts, ku_ctx_merge_state on either side, ku_sparse_close_unit,
+ *     ku_ctx_replace_calls), replaces what the kernels read (load / adopt / add / swap / prefetch a database, the
+ *     taxonomy, ku_ctx_enable_exact, enabling or disabling the emulation) or classifies by another path (ku_classify_batch,
+ *     _rle, the device and staged entry points, ku_batch_*), and every ku_mgpu_* that classifies, reduces, loads or
+ *     changes state while one of the group's rank contexts has batches in flight;
+ *   - wait for all of the context's streams: ku_ctx_synchronize, ku_ctx_destroy (and ku_mgpu_destroy through them);
+ *   - answer as on an idle context: the queries (dimensions, layout, values, count_taxons, mem_info, sparse state, device
+ *     pointers, the group's flags and counts), ku_fetch_runs (the batch finished last) and the two steps themselves. */
 int ku_classify_batch_rle_enqueue(ku_ctx *ctx, const char *seqs, uint64_t n_bytes, const uint64_t *seq_off,
                                   const uint32_t *seq_len, uint64_t n_reads, const ku_opts *opts, uint32_t *calls,
                                   uint32_t *hits, uint64_t *run_off, uint32_t *run_cnt, ku_run *runs, uint64_t runs_cap);
@@ -347,6 +357,7 @@ void ku_batch_destroy(ku_batch *b);
  * sees what a single GPU would have after all chunks.  ku_ctx_merge_state adds the per-taxon state the other GPU's passes
  * booked (registers MAX, n_kmers SUM, n_reads SUM) to dst's -- once, at the end of the run. */
 int ku_batch_absorb(ku_ctx *ctx, ku_batch *dst, const ku_batch *src);
+/* KU_ESTATE while either context has batches in flight (their counters are still being written) */
 int ku_ctx_merge_state(ku_ctx *dst, ku_ctx *src);
 
 /* Same on device-resident buffers, asynchronous on `stream` (a hipStream_t
@@ -388,6 +399,9 @@ int ku_lookup_device(ku_ctx *ctx, const void *d_seqs, uint64_t n_bytes, const ku
 int ku_resolve_device(ku_ctx *ctx, const void *d_seqs, const uint64_t *d_seq_off, const uint32_t *d_seq_len,
                       uint64_t n_reads, const ku_opts *opts, uint32_t *d_calls, uint32_t *d_taxa,
                       uint32_t *d_hits, void *stream);
+/* returns once all work queued on the context is complete, on every one of its streams: its own, those of the batches in
+ * flight (kernels, uploads, copies back) and ku_fetch_runs'.  The batches stay in flight: ku_classify_batch_rle_finish still
+ * settles each one and returns what it would have returned. */
 int ku_ctx_synchronize(ku_ctx *ctx);
 /* Measurement aid (bench.py roofline): runs the scan + minimizer + idx stages only
  * and returns, for the k-mers this context owns, stats_out[4] = { lookups,

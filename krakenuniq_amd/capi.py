@@ -592,7 +592,12 @@ class Ctx:
         return {"lookups": int(out[0]), "sum_ceil_log2": int(out[1]), "nonempty": int(out[2]), "sum_nb": int(out[3])}
 
     def synchronize(self):
+        """waits for everything queued on the context, batches in flight included (they stay in flight until rle_finish)"""
         _chk(lib().ku_ctx_synchronize(self.h), "ku_ctx_synchronize")
+
+    def merge_state(self, src: "Ctx"):
+        """adds src's per-taxon state to this context's (ku_ctx_merge_state: registers MAX, n_kmers / n_reads SUM)"""
+        _chk(lib().ku_ctx_merge_state(self.h, src.h), "ku_ctx_merge_state")
 
     def counts(self):
         d = CountsDims()

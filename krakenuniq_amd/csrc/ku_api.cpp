@@ -404,11 +404,23 @@ static void ctx_free_tax(ku_ctx *ctx) {
   ctx->tax_set = false;
 }
 
+// Waits for everything queued on any of the context's streams: its own, the two kernel streams and the copy streams of the
+// batches in flight, ku_fetch_runs' stream and the prefetch stream.  Leaves rle_in_flight alone: _finish still settles
+// each batch (its event is complete by then) and returns what it would have returned.
+int ctx_sync_all_streams(ku_ctx *ctx) {
+  int st = KU_OK;
+  for (hipStream_t s : {ctx->stream, ctx->k_streams[0], ctx->k_streams[1], ctx->h2d_stream, ctx->d2h_stream, ctx->fetch_stream, ctx->pf.stream})
+    if (s && hipStreamSynchronize(s) != hipSuccess && st == KU_OK) st = fail(KU_EHIP, "ku_ctx_synchronize: a stream of the context failed");
+  return st;
+}
+
 extern "C" void ku_ctx_destroy(ku_ctx *ctx) {
   if (!ctx) return;
   rle_times_print();
   (void)hipSetDevice(ctx->device);
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  // batches may still be in flight: their kernels and copies into the caller's memory run on the other streams, and they
+  // use the buffers freed below
+  (void)ctx_sync_all_streams(ctx);
   ctx_free_db(ctx);
   ctx_free_tax(ctx);
   for (DevBuf *b : {&ctx->b_seqs, &ctx->b_off, &ctx->b_len, &ctx->b_calls, &ctx->b_taxa, &ctx->b_hits, &ctx->b_ws, &ctx->b_runs,
@@ -500,6 +512,7 @@ int store_upload(ku_ctx *ctx, DbStore &d, const ku_db *db, uint64_t bin_lo, uint
 
 extern "C" int ku_ctx_load_db(ku_ctx *ctx, const ku_db *db, uint64_t bin_lo, uint64_t bin_hi) {
   if (!ctx || !db) return fail(KU_EINVAL, "ku_ctx_load_db: null argument");
+  KU_TRY(rle_idle(ctx, "ku_ctx_load_db"));
   if (bin_lo > bin_hi || bin_hi > db->info.n_bins) return fail(KU_EINVAL, "bin range out of bounds");
   KU_TRY(ctx_activate(ctx));
   ctx_free_tax(ctx);
@@ -513,6 +526,7 @@ bool store_whole(const DbStore &d) { return d.db.bin_lo == 0 && d.db.bin_hi == (
 
 extern "C" int ku_ctx_add_db(ku_ctx *ctx, const ku_db *db) {
   if (!ctx || !db) return fail(KU_EINVAL, "ku_ctx_add_db: null argument");
+  KU_TRY(rle_idle(ctx, "ku_ctx_add_db"));
   if (!ctx->db_loaded) return fail(KU_ESTATE, "load the first database before adding further ones");
   if (ctx->tax_set) return fail(KU_ESTATE, "add every database before the taxonomy is set");
   if (db->info.k != ctx->m.db.k)  // classify.cpp:199-208 "Different k-mer sizes in databases"
@@ -529,6 +543,7 @@ extern "C" int ku_ctx_add_db(ku_ctx *ctx, const ku_db *db) {
 extern "C" int ku_ctx_adopt_db(ku_ctx *ctx, void *d_pairs, uint64_t n_pairs, const uint64_t *d_offsets, uint32_t k,
                                uint32_t nt, uint32_t idx_type, uint64_t bin_lo, uint64_t bin_hi) {
   if (!ctx || (!d_pairs && n_pairs) || !d_offsets) return fail(KU_EINVAL, "ku_ctx_adopt_db: null argument");
+  KU_TRY(rle_idle(ctx, "ku_ctx_adopt_db"));
   if (k < 1 || k > 31 || nt < 1 || nt > 15 || nt > k || (idx_type != 1 && idx_type != 2) || bin_lo > bin_hi ||
       bin_hi > (1ull << (2 * nt)))
     return fail(KU_EINVAL, "ku_ctx_adopt_db: bad geometry");
@@ -655,6 +670,7 @@ int store_finalize(ku_ctx *ctx, DbStore &d, hipStream_t stream, uint32_t *d_scal
 
 extern "C" int ku_ctx_set_taxonomy(ku_ctx *ctx, const ku_tax *tax, const uint32_t *all_values, uint64_t n_values) {
   if (!ctx || !tax) return fail(KU_EINVAL, "ku_ctx_set_taxonomy: null argument");
+  KU_TRY(rle_idle(ctx, "ku_ctx_set_taxonomy"));
   if (!ctx->db_loaded) return fail(KU_ESTATE, "load a database before the taxonomy");
   if (ctx->tax_set) return fail(KU_ESTATE, "taxonomy already set for this shard (values are remapped once)");
   KU_TRY(ctx_activate(ctx));
@@ -744,7 +760,7 @@ extern "C" int ku_ctx_set_taxonomy(ku_ctx *ctx, const ku_tax *tax, const uint32_
 
 extern "C" int ku_ctx_reset_counts(ku_ctx *ctx) {
   if (!ctx || !ctx->tax_set) return fail(KU_ESTATE, "taxonomy not set");
-  if (ctx->rle_in_flight) return fail(KU_ESTATE, "ku_ctx_reset_counts: batches are in flight (ku_classify_batch_rle_finish first)");
+  KU_TRY(rle_idle(ctx, "ku_ctx_reset_counts"));
   KU_TRY(ctx_activate(ctx));
   HIP_TRY(hipMemsetAsync(ctx->cnt.registers, 0, (size_t)ctx->tax.n_slots * KU_HLL_M, ctx->stream));
   HIP_TRY(hipMemsetAsync(ctx->cnt.n_kmers, 0, (size_t)ctx->tax.n_slots * 8, ctx->stream));
@@ -782,6 +798,7 @@ int sparse_pass(ku_ctx *ctx, const void *d_seqs, const uint64_t *d_off, const ui
 
 extern "C" int ku_ctx_enable_exact(ku_ctx *ctx, uint32_t capacity_log2) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_ctx_enable_exact"));
   if (capacity_log2 < 10 || capacity_log2 > 36) return fail(KU_EINVAL, "ku_ctx_enable_exact: capacity_log2 out of range (10..36)");
   if (ctx->d_exact_set) { (void)hipFree(ctx->d_exact_set); ctx->d_exact_set = nullptr; }
   if (ctx->d_exact_unique) { (void)hipFree(ctx->d_exact_unique); ctx->d_exact_unique = nullptr; }
@@ -799,6 +816,7 @@ extern "C" int ku_ctx_enable_exact(ku_ctx *ctx, uint32_t capacity_log2) {
 
 extern "C" int ku_counts_export_exact(ku_ctx *ctx, uint64_t *unique_kmers) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_counts_export_exact"));
   if (!ctx->d_exact_set) return fail(KU_ESTATE, "exact counting is not enabled (ku_ctx_enable_exact)");
   if (!unique_kmers) return fail(KU_EINVAL, "ku_counts_export_exact: null buffer");
   HIP_TRY(hipStreamSynchronize(ctx->stream));

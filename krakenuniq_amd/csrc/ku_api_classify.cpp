@@ -13,6 +13,7 @@ int check_ready(ku_ctx *ctx) {
 extern "C" int ku_lookup_device(ku_ctx *ctx, const void *d_seqs, uint64_t n_bytes, const ku_opts *opts,
                                 uint32_t *d_taxa, void *stream) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_lookup_device"));
   if (n_bytes && (!d_seqs || !d_taxa)) return fail(KU_EINVAL, "ku_lookup_device: null buffer");
   const uint32_t flags = opts ? opts->flags : 0;
   // quick mode counts only the scanned prefix of each read -> accounted in the resolve stage
@@ -97,6 +98,7 @@ int ku_exact_owned_step(ku_ctx *ctx, const void *d_seqs, const uint64_t *d_off, 
 extern "C" int ku_lookup_stats_device(ku_ctx *ctx, const void *d_seqs, uint64_t n_bytes, uint64_t *stats_out,
                                       void *stream) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_lookup_stats_device"));
   if (!stats_out || (n_bytes && !d_seqs)) return fail(KU_EINVAL, "ku_lookup_stats_device: null argument");
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   unsigned long long *d_stats = (unsigned long long *)(ctx->d_scalar + 8);  // 32 bytes at offset 32
@@ -112,6 +114,7 @@ extern "C" int ku_resolve_device(ku_ctx *ctx, const void *d_seqs, const uint64_t
                                  uint64_t n_reads, const ku_opts *opts, uint32_t *d_calls, uint32_t *d_taxa,
                                  uint32_t *d_hits, void *stream) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_resolve_device"));
   if (n_reads && (!d_seq_off || !d_seq_len || !d_calls || !d_taxa)) return fail(KU_EINVAL, "ku_resolve_device: null buffer");
   const uint32_t flags = opts ? opts->flags : 0;
   if ((flags & KU_F_QUICK) && !d_seqs) return fail(KU_EINVAL, "quick mode needs the sequence buffer");
@@ -206,6 +209,7 @@ int classify_device_impl(ku_ctx *ctx, const void *d_seqs, uint64_t n_bytes, cons
 extern "C" int ku_classify_batch_device(ku_ctx *ctx, const void *d_seqs, uint64_t n_bytes, const uint64_t *d_seq_off,
                                         const uint32_t *d_seq_len, uint64_t n_reads, const ku_opts *opts,
                                         uint32_t *d_calls, uint32_t *d_taxa, uint32_t *d_hits, void *stream) {
+  if (ctx) KU_TRY(rle_idle(ctx, "ku_classify_batch_device"));
   return classify_device_impl(ctx, d_seqs, n_bytes, d_seq_off, d_seq_len, n_reads, opts, d_calls, d_taxa, d_hits, stream, nullptr, nullptr);
 }
 
@@ -213,6 +217,7 @@ extern "C" int ku_classify_batch(ku_ctx *ctx, const char *seqs, uint64_t n_bytes
                                  const uint32_t *seq_len, uint64_t n_reads, const ku_opts *opts, uint32_t *calls,
                                  uint32_t *taxa, uint32_t *hits) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_classify_batch"));
   if ((n_bytes && !seqs) || (n_reads && (!seq_off || !seq_len || !calls))) return fail(KU_EINVAL, "ku_classify_batch: null buffer");
   if (n_reads == 0) return KU_OK;
   ku_opts o = opts ? *opts : ku_opts{0, 1, 0, 0};

@@ -6,6 +6,7 @@ extern "C" int ku_ctx_prefetch_shard(ku_ctx *ctx, const ku_db *db, uint64_t bin_
   // Safe to call from a second host thread while the first one runs lookups on the resident shard: it works on its own
   // stream, its own scratch and its own store and only reads the (frozen) slot table of the context.
   if (!ctx || !db) return fail(KU_EINVAL, "ku_ctx_prefetch_shard: null argument");
+  KU_TRY(rle_idle(ctx, "ku_ctx_prefetch_shard"));
   if (!ctx->db_loaded || !ctx->tax_set) return fail(KU_ESTATE, "ku_ctx_prefetch_shard: load a shard and the taxonomy first");
   if (bin_lo > bin_hi || bin_hi > db->info.n_bins) return fail(KU_EINVAL, "bin range out of bounds");
   if (!ctx->extra.empty()) return fail(KU_EUNSUP, "chunked runs use one database (as the reference's: classify.cpp:639)");
@@ -32,6 +33,7 @@ extern "C" int ku_ctx_prefetch_shard(ku_ctx *ctx, const ku_db *db, uint64_t bin_
 
 extern "C" int ku_ctx_swap_shard(ku_ctx *ctx, const ku_db *db, uint64_t bin_lo, uint64_t bin_hi) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_ctx_swap_shard"));
   if (!db) return fail(KU_EINVAL, "ku_ctx_swap_shard: null argument");
   if (bin_lo > bin_hi || bin_hi > db->info.n_bins) return fail(KU_EINVAL, "bin range out of bounds");
   if (!ctx->extra.empty()) return fail(KU_EUNSUP, "chunked runs use one database (as the reference's: classify.cpp:639)");
@@ -79,6 +81,7 @@ extern "C" void ku_batch_destroy(ku_batch *b) {
 extern "C" int ku_batch_create(ku_ctx *ctx, const char *seqs, uint64_t n_bytes, const uint64_t *seq_off,
                                const uint32_t *seq_len, uint64_t n_reads, ku_batch **out) {
   if (!ctx || !out || (n_bytes && !seqs) || (n_reads && (!seq_off || !seq_len))) return fail(KU_EINVAL, "ku_batch_create: null argument");
+  KU_TRY(rle_idle(ctx, "ku_batch_create"));
   *out = nullptr;
   KU_TRY(ctx_activate(ctx));
   uint32_t max_len = 0;
@@ -105,6 +108,7 @@ extern "C" int ku_batch_create(ku_ctx *ctx, const char *seqs, uint64_t n_bytes, 
 
 extern "C" int ku_batch_absorb(ku_ctx *ctx, ku_batch *dst, const ku_batch *src) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_batch_absorb"));
   if (!dst || !src || dst->ctx != ctx || !src->ctx) return fail(KU_EINVAL, "ku_batch_absorb: null argument / batch of another context");
   if (dst->n_bytes != src->n_bytes || dst->n_reads != src->n_reads) return fail(KU_EINVAL, "ku_batch_absorb: the batches hold different reads");
   if (dst->finished || src->finished) return fail(KU_ESTATE, "ku_batch_absorb: a batch was already finished");
@@ -128,6 +132,9 @@ extern "C" int ku_batch_absorb(ku_ctx *ctx, ku_batch *dst, const ku_batch *src) 
 extern "C" int ku_ctx_merge_state(ku_ctx *dst, ku_ctx *src) {
   KU_TRY(check_ready(dst));
   KU_TRY(check_ready(src));
+  // both sides: src's counters may still be written by its batches, dst's by its own
+  KU_TRY(rle_idle(dst, "ku_ctx_merge_state (dst)"));
+  KU_TRY(rle_idle(src, "ku_ctx_merge_state (src)"));
   if (dst == src) return KU_OK;
   if (dst->tax.n_slots != src->tax.n_slots || dst->tax.n_nodes != src->tax.n_nodes) return fail(KU_EINVAL, "ku_ctx_merge_state: the contexts number their taxa differently");
   if (hipSetDevice(src->device) != hipSuccess || hipStreamSynchronize(src->stream) != hipSuccess) return fail(KU_EHIP, "ku_ctx_merge_state: the source context's stream failed");
@@ -157,6 +164,7 @@ extern "C" int ku_ctx_merge_state(ku_ctx *dst, ku_ctx *src) {
 
 extern "C" int ku_batch_lookup(ku_ctx *ctx, ku_batch *b, const ku_opts *opts) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_batch_lookup"));
   if (!b || b->ctx != ctx) return fail(KU_EINVAL, "ku_batch_lookup: batch of another context");
   if (b->finished) return fail(KU_ESTATE, "ku_batch_lookup: the batch was already finished");
   ku_opts o = opts ? *opts : ku_opts{0, 1, 0, 0};
@@ -169,6 +177,7 @@ extern "C" int ku_batch_lookup(ku_ctx *ctx, ku_batch *b, const ku_opts *opts) {
 extern "C" int ku_batch_finish(ku_ctx *ctx, ku_batch *b, const ku_opts *opts, uint32_t *calls, uint32_t *hits,
                                uint64_t *run_off, uint32_t *run_cnt, uint64_t *n_runs) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_batch_finish"));
   if (!b || b->ctx != ctx) return fail(KU_EINVAL, "ku_batch_finish: batch of another context");
   if (!n_runs || (b->n_reads && (!calls || !run_off || !run_cnt))) return fail(KU_EINVAL, "ku_batch_finish: null buffer");
   if (b->finished) return fail(KU_ESTATE, "ku_batch_finish: the batch was already finished");
@@ -217,6 +226,5 @@ extern "C" int ku_batch_finish(ku_ctx *ctx, ku_batch *b, const ku_opts *opts, ui
 extern "C" int ku_ctx_synchronize(ku_ctx *ctx) {
   if (!ctx) return fail(KU_EINVAL, "null context");
   KU_TRY(ctx_activate(ctx));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return KU_OK;
+  return ctx_sync_all_streams(ctx);
 }

@@ -14,6 +14,7 @@ extern "C" int ku_counts_export(ku_ctx *ctx, uint32_t *slot_taxid, uint64_t *n_k
                                 uint32_t *node_taxid, uint64_t *n_reads) {
   if (!ctx) return fail(KU_EINVAL, "null context");
   if (!ctx->tax_set) return fail(KU_ESTATE, "taxonomy not set");
+  KU_TRY(rle_idle(ctx, "ku_counts_export"));
   KU_TRY(ctx_activate(ctx));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   const size_t ns = ctx->tax.n_slots, nn = ctx->tax.n_nodes;

@@ -248,6 +248,7 @@ extern "C" int ku_classify_batch_device_rle(ku_ctx *ctx, const void *d_seqs, uin
                                             ku_run *d_runs, uint64_t runs_cap, uint64_t *d_run_off, uint32_t *d_run_cnt,
                                             uint64_t *d_n_runs, void *stream) {
   KU_TRY(check_ready(ctx));
+  KU_TRY(rle_idle(ctx, "ku_classify_batch_device_rle"));
   if (!d_n_runs || (n_reads && (!d_seqs || !d_seq_off || !d_seq_len || !d_calls || !d_runs || !d_run_off || !d_run_cnt)))
     return fail(KU_EINVAL, "ku_classify_batch_device_rle: null buffer");
   const ku_opts o = opts ? *opts : ku_opts{0, 1, 0, 0};
@@ -644,9 +645,11 @@ static int rle_job_finish(ku_ctx *ctx, RleJob &j, uint64_t *n_runs, bool *classi
   return KU_OK;
 }
 
-int rle_drain_kernels(ku_ctx *ctx) {
+// every batch in flight is through its kernels AND its copies back (its `done` event): the copy of the run-wide set's size
+// into the batch's totals is among those copies
+int rle_drain_batches(ku_ctx *ctx) {
   for (RleJob &q : ctx->rle)
-    if (q.busy && q.kernels_done) HIP_TRY(hipEventSynchronize(q.kernels_done));
+    if (q.busy && q.done) HIP_TRY(hipEventSynchronize(q.done));
   return KU_OK;
 }
 

@@ -49,15 +49,19 @@ extern "C" int ku_ctx_enable_sparse(ku_ctx *ctx, uint64_t work_unit_nt, uint32_t
 // room in the run-wide (slot, encoding) set for `incoming` more entries at load <= 1/2: a larger table takes over when
 // the current one could fill (the set only grows with the distinct k-mers of the taxa that stay sparse -- on a run of
 // many taxa that is most of what the reads hold)
-// the kernels of every batch in flight are through (they run on streams of their own: what is about to replace a table they
-// write to -- the run-wide set growing -- waits for them on the host; rare)
+// every batch in flight is through, its copies back included (its kernels run on streams of their own: what is about to
+// replace a table they write to -- the run-wide set growing -- waits for them on the host; rare).
+// Invariant that `g_count = max(g_count, h_tot[1])` in _finish relies on: the device's size of the set (d.g_count) never
+// decreases while a batch in flight may still copy it into its totals.  The rehash below zeroes it and counts again; it
+// only runs once those copies have all landed, and it sets the host's g_count to the full count it finds, so a batch
+// finished later can only report that size or a larger one.
 
 int sparse_reserve_global(ku_ctx *ctx, uint64_t incoming, hipStream_t s) {
   ku_ctx::Sparse &sp = ctx->sp;
   KuSparseDev &d = sp.dev;
   const uint64_t need = 2 * (sp.g_count + incoming);
   if (need <= d.g_mask + 1) return KU_OK;
-  KU_TRY(rle_drain_kernels(ctx));
+  KU_TRY(rle_drain_batches(ctx));
   uint64_t cells = (d.g_mask + 1) * 2;
   while (cells < need) cells *= 2;
   const char *cap_env = getenv("KU_SPARSE_MAX_LOG2");  // test hook: a small ceiling stands in for a full device

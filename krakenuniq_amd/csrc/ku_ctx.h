@@ -257,6 +257,7 @@ struct ku_batch {
 
 // ---- functions one area calls in another (defined in the file named behind them)
 int ctx_activate(ku_ctx *ctx);  // ku_api.cpp
+int ctx_sync_all_streams(ku_ctx *ctx);  // ku_api.cpp
 void store_free(DbStore &d);  // ku_api.cpp
 void ctx_drop_count_cache(ku_ctx *ctx);  // ku_api.cpp
 void ctx_free_sparse(ku_ctx *ctx);  // ku_api.cpp
@@ -275,4 +276,4 @@ int sparse_tail_to_carry(ku_ctx *ctx);  // ku_api_rle.cpp
 int sparse_tail_close(ku_ctx *ctx);  // ku_api_rle.cpp
 void rle_times_print();  // ku_api_rle.cpp
 int rle_idle(const ku_ctx *ctx, const char *who);  // ku_api_rle.cpp
-int rle_drain_kernels(ku_ctx *ctx);  // ku_api_rle.cpp
+int rle_drain_batches(ku_ctx *ctx);  // ku_api_rle.cpp

@@ -616,6 +616,15 @@ int comm_scatter_slices(ku_mgpu *m, ku_mgpu::Rank &r, int st, void *buf, const u
 }
 
 bool single_process(const ku_mgpu *m) { return m->first_rank == 0 && m->n_local == m->world; }
+
+// A rank context (ku_mgpu_ctx) with batches of ku_classify_batch_rle_enqueue in flight: whatever classifies, reduces, loads or
+// changes state over the group answers KU_ESTATE, before any rank starts (a collective must not begin on some ranks only)
+int ranks_idle(const ku_mgpu *m, const char *who) {
+  for (const auto &r : m->ranks)
+    if (r.ctx && ku_classify_batch_rle_in_flight(r.ctx))
+      return mfail(KU_ESTATE, std::string(who) + ": rank " + std::to_string(r.rank) + " has batches in flight (ku_classify_batch_rle_finish first)");
+  return KU_OK;
+}
 }  // namespace
 
 // ---------------------------------------------------------------------------- life cycle
@@ -736,6 +745,7 @@ extern "C" int ku_mgpu_step_times(ku_mgpu *m, uint32_t local_index, double *out)
 
 extern "C" int ku_mgpu_set_taxonomy(ku_mgpu *m, const ku_tax *tax) {
   if (!m || !tax) return mfail(KU_EINVAL, "ku_mgpu_set_taxonomy: null argument");
+  M_TRY(ranks_idle(m, "ku_mgpu_set_taxonomy"));
   M_TRY(run_all(m, [&](ku_mgpu::Rank &r) -> int {
     uint64_t n = 0;
     int st = ku_ctx_db_values(r.ctx, nullptr, &n);
@@ -776,6 +786,7 @@ extern "C" int ku_mgpu_set_taxonomy(ku_mgpu *m, const ku_tax *tax) {
 
 extern "C" int ku_mgpu_load_dbs(ku_mgpu *m, const ku_db *const *dbs, uint32_t n_dbs, const ku_tax *tax) {
   if (!m || !dbs || !n_dbs || !tax) return mfail(KU_EINVAL, "ku_mgpu_load_dbs: null argument");
+  M_TRY(ranks_idle(m, "ku_mgpu_load_dbs"));
   if (n_dbs == 1) return ku_mgpu_load(m, dbs[0], tax);
   // several databases are searched one after the other per k-mer, the first hit wins (classify.cpp:928-936): with the
   // first database cut into shards a later one could not tell whether another rank had found the k-mer already -- the
@@ -794,6 +805,7 @@ extern "C" int ku_mgpu_load_dbs(ku_mgpu *m, const ku_db *const *dbs, uint32_t n_
 
 extern "C" int ku_mgpu_load(ku_mgpu *m, const ku_db *db, const ku_tax *tax) {
   if (!m || !db || !tax) return mfail(KU_EINVAL, "ku_mgpu_load: null argument");
+  M_TRY(ranks_idle(m, "ku_mgpu_load"));
   ku_db_info info;
   M_TRY(ku_db_get_info(db, &info));
   std::vector<uint64_t> bounds(m->world + 1);
@@ -809,6 +821,7 @@ extern "C" int ku_mgpu_load(ku_mgpu *m, const ku_db *db, const ku_tax *tax) {
 // ---------------------------------------------------------------------------- report modes over the group
 extern "C" int ku_mgpu_enable_sparse(ku_mgpu *m, uint64_t work_unit_nt, uint32_t global_log2) {
   if (!m) return mfail(KU_EINVAL, "ku_mgpu_enable_sparse: null argument");
+  M_TRY(ranks_idle(m, "ku_mgpu_enable_sparse"));
   if (!m->tax_set) return mfail(KU_ESTATE, "ku_mgpu_enable_sparse: load the database and the taxonomy first");
   if (!single_process(m)) return mfail(KU_EUNSUP, "the sparse-mode emulation over several GPUs needs the group in one process");
   if (work_unit_nt == 0) return mfail(KU_EUNSUP, "ku_mgpu_enable_sparse: a work unit size is needed (the ranks take whole units)");
@@ -821,6 +834,7 @@ extern "C" int ku_mgpu_enable_sparse(ku_mgpu *m, uint64_t work_unit_nt, uint32_t
 }
 extern "C" int ku_mgpu_sparse_close_unit(ku_mgpu *m) {
   if (!m) return mfail(KU_EINVAL, "ku_mgpu_sparse_close_unit: null argument");
+  M_TRY(ranks_idle(m, "ku_mgpu_sparse_close_unit"));
   if (!m->sparse) return KU_OK;
   if (m->open_rank >= 0) {
     ku_mgpu::Rank &r = m->ranks[m->open_rank];
@@ -842,6 +856,7 @@ extern "C" int ku_mgpu_sparse_state(const ku_mgpu *m) {
 }
 extern "C" int ku_mgpu_enable_exact(ku_mgpu *m, uint32_t capacity_log2) {
   if (!m) return mfail(KU_EINVAL, "ku_mgpu_enable_exact: null argument");
+  M_TRY(ranks_idle(m, "ku_mgpu_enable_exact"));
   if (!m->tax_set) return mfail(KU_ESTATE, "ku_mgpu_enable_exact: load the database and the taxonomy first");
   // owner-computes: a k-mer is put into the set of the rank that owns its minimizer bin, so the ranks' sets are disjoint
   // and the distinct counts add up.  Replicas would see the same k-mer on several ranks.
@@ -1221,6 +1236,7 @@ int rank_step_routed(ku_mgpu *m, ku_mgpu::Rank &r, int st, void *d_seqs, uint64_
 extern "C" int ku_mgpu_step_device(ku_mgpu *m, const ku_mgpu_dev_batch *local, uint64_t n_bytes, uint64_t n_reads,
                                    const uint64_t *read_bounds, const uint64_t *pos_bounds, const ku_opts *opts) {
   if (!m || !local || !read_bounds || !pos_bounds) return mfail(KU_EINVAL, "ku_mgpu_step_device: null argument");
+  M_TRY(ranks_idle(m, "ku_mgpu_step_device"));
   if (!m->tax_set) return mfail(KU_ESTATE, "ku_mgpu_step_device: load the database and the taxonomy first");
   if (m->flags & KU_MGPU_REPLICAS) return mfail(KU_EINVAL, "ku_mgpu_step_device is the sharded step; replicas classify through their own contexts");
   const ku_opts o = opts ? *opts : ku_opts{0, 1, 0, 0};
@@ -1242,6 +1258,7 @@ extern "C" int ku_mgpu_classify_batch_rle(ku_mgpu *m, const char *seqs, uint64_t
                                           uint32_t *hits, uint64_t *run_off, uint32_t *run_cnt, uint64_t *n_runs) {
   if (!m || !n_runs || (n_bytes && !seqs) || (n_reads && (!seq_off || !seq_len || !calls || !run_off || !run_cnt)))
     return mfail(KU_EINVAL, "ku_mgpu_classify_batch_rle: null argument");
+  M_TRY(ranks_idle(m, "ku_mgpu_classify_batch_rle"));
   if (!single_process(m)) return mfail(KU_EUNSUP, "host batches go through a single-process group");
   if (!m->tax_set) return mfail(KU_ESTATE, "ku_mgpu_classify_batch_rle: load the database and the taxonomy first");
   *n_runs = 0;
@@ -1415,6 +1432,7 @@ extern "C" int ku_mgpu_fetch_runs(ku_mgpu *m, ku_run *runs, uint64_t n_runs) {
 
 extern "C" int ku_mgpu_reduce_state(ku_mgpu *m, void *const *streams) {
   if (!m) return mfail(KU_EINVAL, "ku_mgpu_reduce_state: null argument");
+  M_TRY(ranks_idle(m, "ku_mgpu_reduce_state"));
   if (!m->tax_set) return mfail(KU_ESTATE, "ku_mgpu_reduce_state: no taxonomy set");
   if (m->reduced) return mfail(KU_ESTATE, "ku_mgpu_reduce_state: the state is reduced already (another call would add the counters again)");
   M_TRY(run_all(m, [&](ku_mgpu::Rank &r) -> int {

@@ -37,6 +37,31 @@ def test_library_exports_every_declared_symbol():
     assert L.ku_abi_version() == 1
 
 
+def test_every_context_entry_point_has_an_in_flight_contract():
+    """tests/inflight_contract.py: one row per prototype whose first parameter is ku_ctx * or ku_mgpu *, and no row without
+    one -- a new entry point fails here until someone has decided what it does while batches are in flight"""
+    import inflight_contract as ic
+
+    hdr = open(os.path.join(ROOT, "include", "krakenuniq_amd.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    protos = re.findall(r"\b(ku_[a-z0-9_]+)\s*\(\s*(?:const\s+)?(ku_ctx|ku_mgpu)\s*\*", hdr)
+    names = [n for n, _ in protos]
+    assert len(names) == len(set(names)), "a prototype is declared twice"
+    assert len(names) >= 60
+    assert sorted(set(names) - set(ic.CONTRACT)) == [], "entry points without an in-flight row"
+    assert sorted(set(ic.CONTRACT) - set(names)) == [], "rows that name no ku_ctx * / ku_mgpu * prototype"
+    for name, (behaviour, reason) in ic.CONTRACT.items():
+        assert behaviour in (ic.REFUSE, ic.WAIT, ic.ALLOWED), name
+        assert reason.strip() and "\n" not in reason, name
+    # the life cycle waits, the two steps and the queries the header promises stay allowed, what reads or resets the run refuses
+    assert ic.rows(ic.WAIT) == ["ku_ctx_destroy", "ku_ctx_synchronize", "ku_mgpu_destroy"]
+    for n in ("ku_counts_export", "ku_counts_export_exact", "ku_ctx_merge_state", "ku_ctx_reset_counts", "ku_ctx_report",
+              "ku_sparse_export", "ku_sparse_close_unit", "ku_ctx_replace_calls", "ku_classify_batch_rle", "ku_mgpu_reduce_state"):
+        assert ic.CONTRACT[n][0] == ic.REFUSE, n
+    for n in ("ku_classify_batch_rle_enqueue", "ku_classify_batch_rle_finish", "ku_classify_batch_rle_in_flight", "ku_fetch_runs"):
+        assert ic.CONTRACT[n][0] == ic.ALLOWED, n
+
+
 def test_no_cpu_fallback_without_gpu():
     if capi.lib().ku_device_count() > 0:
         pytest.skip("GPU present")
