@@ -90,6 +90,54 @@ int ku_db_chunk_plan(const ku_db *db, uint64_t max_bytes, uint64_t *bin_bounds, 
 int ku_db_sort_files(int device, const char *in_path, const char *out_kdb_path, const char *out_idx_path, uint32_t nt,
                      int zero_vals);
 
+/* The k-mer set of a library, straight to the sorted database (scripts/build_db.sh:140-146 -- jellyfish count / merge /
+ * dump into database.jdb, check_for_jellyfish.sh -- and :201, db_sort -z): ku_kmerdb_add takes one FASTA record's sequence
+ * (line breaks removed; any byte outside ACGTacgt makes the windows that cover it ambiguous, src/krakenutil.cpp:252-263),
+ * extracts its canonical k-mers on the device and keeps the distinct ones; ku_kmerdb_end_pass appends them in (minimizer
+ * bin key, k-mer) order, values 0, to out_kdb_path and their bins' offsets to out_idx_path; ku_kmerdb_finish closes both
+ * files: byte for byte what db_sort -z writes from a Jellyfish list of the same k-mers (src/db_sort.cpp:34-128,
+ * KrakenDB::make_index, src/krakendb.cpp:118-148).  1 <= nt <= 15, nt <= k <= 31.
+ *
+ * n_passes (1 .. 4^nt) splits the bin keys [0, 4^nt) into ranges [p * 4^nt / n_passes, (p + 1) * 4^nt / n_passes): pass p
+ * keeps only the k-mers whose bin key lies in range p, so the caller feeds the SAME records n_passes times, a
+ * ku_kmerdb_end_pass after each round.  That is how a library whose distinct k-mers do not fit the device is built.
+ *
+ * device_bytes is the working-set budget of the collection (0: half of the HBM that is free at ku_kmerdb_open; below
+ * KU_KMERDB_MIN_BYTES: KU_EINVAL): an upload segment of min(64 MiB, device_bytes / 64) bytes, rounded down to 1 KiB, and two
+ * k-mer buffers of capacity = (device_bytes - segment) / 16 k-mers each.  A full buffer is sorted, made unique and merged
+ * into the pass's distinct set, which shares the buffer; every budget from the minimum up gives the same files.  The set
+ * of a pass has to leave 1/64 of the capacity free: KU_ENOMEM otherwise (ku_last_error names -P).  Records longer than a
+ * segment are cut with k - 1 bytes of overlap.  ku_kmerdb_end_pass needs 56 bytes per distinct k-mer of the pass and 16 per bin
+ * of its range for a moment (where the device is that full, one of the k-mer buffers is given back first).  Sizes: a buffer
+ * may hold more than 2^32 k-mers.  rocPRIM's radix sort and unique take 64-bit sizes and batch inside; its merge takes them
+ * but works on 32-bit sums and indices, so the set and the new k-mers are merged in pieces cut at key boundaries, at most
+ * min(2^30, capacity / 4) k-mers of either side per call (checked on the host before every call).
+ *
+ * Call order: add* end_pass, n_passes times, then finish; anything else is KU_EINVAL, and so is every call after one that
+ * failed.  ku_kmerdb_finish: KU_EDATA when the input held no k-mer ("no k-mers in the input"); key_ct may be null.
+ * ku_kmerdb_close removes the files of a build that ku_kmerdb_finish did not complete.  ku_kmerdb_get_stats: what the pass
+ * ended last did, and the run's totals. */
+#define KU_KMERDB_MIN_BYTES 65536
+typedef struct ku_kmerdb ku_kmerdb;
+typedef struct ku_kmerdb_stats {
+  uint64_t capacity;       /* k-mers a buffer holds under the budget */
+  uint64_t segment_bytes;  /* upload segment */
+  uint64_t passes_done;
+  uint64_t windows, candidates, flushes, segments, distinct; /* of the pass ended last: windows scanned, k-mers kept by the
+                                                               * kernel, buffer flushes, segments uploaded, distinct k-mers */
+  uint64_t total_distinct; /* key_ct so far */
+  uint64_t merge_calls;    /* of the pass ended last: pieces in which its flushes merged the new k-mers into the set */
+  double scan_s, flush_s, end_pass_s; /* host clock around the (synchronous) stages, whole run: upload + extraction; sort,
+                                       * unique and merge; bin order, pack and file output */
+} ku_kmerdb_stats;
+int ku_kmerdb_open(int device, uint32_t k, uint32_t nt, uint32_t n_passes, uint64_t device_bytes, const char *out_kdb_path,
+                   const char *out_idx_path, ku_kmerdb **out);
+int ku_kmerdb_add(ku_kmerdb *h, const char *seq, uint64_t len);
+int ku_kmerdb_end_pass(ku_kmerdb *h);
+int ku_kmerdb_finish(ku_kmerdb *h, uint64_t *key_ct);
+int ku_kmerdb_get_stats(const ku_kmerdb *h, ku_kmerdb_stats *out);
+void ku_kmerdb_close(ku_kmerdb *h);
+
 /* ------------------------------------------------------------------ taxonomy
  * Host taxonomy: taxDB text -> entries + Parent_map
  * (taxdb.hpp:563-605 readTaxonomyIndex_, :411-433 createPointers, :383-398 getParentMap). */

@@ -14,6 +14,27 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KU_LIB") or os.path.join(_HERE, "libkrakenuniq_amd.so")  # KU_LIB: tuning experiments, and the tests' -DKU_TEST_HOOKS build
 
+
+def _hw_queues():
+    """The multi-GPU driver runs the rounds of a routed step on two streams per rank, next to the caller's own stream, and the
+    HIP runtime maps all the streams of a process onto GPU_MAX_HW_QUEUES hardware queues (4 unless set).  Streams that share a
+    queue run in issue order: with 4, a rank's second stream and its caller's stream can end up on one queue, so that rounds
+    meant to overlap run one after the other and work that waits for a peer holds up work that does not depend on it.  The
+    binding therefore asks for 8 queues (KU_HW_QUEUES=n: another number, 4 to 32; a larger GPU_MAX_HW_QUEUES is kept).
+    The runtime reads the variable when it initialises, i.e. at the first HIP call of the process: import this module first."""
+    try:
+        have = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+    except ValueError:
+        have = 0
+    try:
+        want = int(os.environ["KU_HW_QUEUES"]) if "KU_HW_QUEUES" in os.environ else max(have, 8)
+    except ValueError:
+        want = max(have, 8)
+    os.environ["GPU_MAX_HW_QUEUES"] = str(min(max(want, 4), 32))
+
+
+_hw_queues()
+
 KU_AMBIG = 0xFFFFFFFF
 KU_HLL_M = 4096
 KU_F_QUICK, KU_F_NO_COUNTS, KU_F_KEEP_SLOTS, KU_F_MERGE_CHUNK = 1, 2, 4, 8
@@ -72,6 +93,12 @@ SIGNATURES = {
     "ku_setlcas_uid_map": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint64)]),
     "ku_setlcas_close": (None, [C.c_void_p]),
     "ku_db_sort_files": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int]),
+    "ku_kmerdb_open": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "ku_kmerdb_add": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "ku_kmerdb_end_pass": (C.c_int, [C.c_void_p]),
+    "ku_kmerdb_finish": (C.c_int, [C.c_void_p, u64p]),
+    "ku_kmerdb_get_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ku_kmerdb_close": (None, [C.c_void_p]),
     "ku_ctx_swap_shard": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "ku_ctx_prefetch_shard": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "ku_ctx_mem_info": (C.c_int, [C.c_void_p, u64p, u64p]),
@@ -822,6 +849,85 @@ def db_sort_files(in_path, out_kdb, out_idx, nt, zero_vals=False, device=0):
     """db_sort on the GPU: Jellyfish-format list -> database.kdb + database.idx"""
     _chk(lib().ku_db_sort_files(device, in_path.encode(), out_kdb.encode(), out_idx.encode(), nt, int(zero_vals)),
          "ku_db_sort_files")
+
+
+class KmerDbStats(C.Structure):  # ku_kmerdb_stats
+    _fields_ = [(n, C.c_uint64) for n in ("capacity", "segment_bytes", "passes_done", "windows", "candidates", "flushes", "segments",
+                                          "distinct", "total_distinct", "merge_calls")] + [(n, C.c_double) for n in ("scan_s", "flush_s", "end_pass_s")]
+
+
+KU_KMERDB_MIN_BYTES = 65536
+
+
+def kmer_db_capacity(device_bytes):
+    """the budget rule of ku_kmerdb_open: (k-mers a collection buffer holds, bytes of an upload segment)"""
+    seg = min(64 << 20, device_bytes // 64) & ~1023
+    return (device_bytes - seg) // 16, seg
+
+
+class KmerDb:
+    """The k-mer set of a library as a sorted database.kdb + database.idx (ku_kmerdb_*):
+
+        with KmerDb(out_kdb, out_idx, k, nt, passes) as b:
+            for _ in range(passes):
+                for s in seqs: b.add(s)
+                b.end_pass()
+            key_ct = b.finish()
+    """
+
+    def __init__(self, out_kdb, out_idx, k, nt, passes=1, device_bytes=0, device=0):
+        self.h = C.c_void_p()
+        self.passes = passes
+        _chk(lib().ku_kmerdb_open(device, k, nt, passes, device_bytes, os.fsencode(out_kdb), os.fsencode(out_idx), C.byref(self.h)),
+             "ku_kmerdb_open")
+
+    def add(self, seq: bytes):
+        _chk(lib().ku_kmerdb_add(self.h, seq, len(seq)), "ku_kmerdb_add")
+
+    def end_pass(self):
+        """ends the pass; returns its statistics (KmerDbStats)"""
+        _chk(lib().ku_kmerdb_end_pass(self.h), "ku_kmerdb_end_pass")
+        return self.stats()
+
+    def stats(self):
+        st = KmerDbStats()
+        _chk(lib().ku_kmerdb_get_stats(self.h, C.byref(st)), "ku_kmerdb_get_stats")
+        return st
+
+    def finish(self):
+        n = C.c_uint64()
+        _chk(lib().ku_kmerdb_finish(self.h, C.byref(n)), "ku_kmerdb_finish")
+        return n.value
+
+    def close(self):
+        if self.h:
+            lib().ku_kmerdb_close(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def kmer_db_files(fasta_seqs, out_kdb, out_idx, k, nt, passes=1, device_bytes=0, device=0):
+    """library sequences (one bytes object per FASTA record, line breaks removed) -> database.kdb + database.idx; returns
+    (key_ct, [KmerDbStats per pass])"""
+    seqs = list(fasta_seqs)
+    per_pass = []
+    with KmerDb(out_kdb, out_idx, k, nt, passes, device_bytes, device) as b:
+        for _ in range(passes):
+            for s in seqs:
+                b.add(s)
+            per_pass.append(b.end_pass())
+        return b.finish(), per_pass
 
 
 def hll_cardinality(registers, n_observed, p=12):

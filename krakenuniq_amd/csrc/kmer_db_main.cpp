@@ -1,0 +1,165 @@
+// kmer_db: library FASTA -> sorted database.kdb + database.idx on the GPU through ku_kmerdb_*.  It stands where the
+// reference's build runs Jellyfish 1 and db_sort (scripts/build_db.sh:140-146 and :201): no k-mer list is written in
+// between, the values are 0 as after db_sort -z, and set_lcas follows as before.  The input goes through the same stage as
+// set_lcas's -F file (plain, .gz / BGZF, .bz2); with -P above 1 it is read once per pass.
+#include <getopt.h>
+#include <sysexits.h>
+#include <unistd.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/krakenuniq_amd.h"
+#include "ku_seqio.h"
+#include "ku_fasta.h"
+
+// the output files once ku_kmerdb_open has created them: a fatal error of the input stage (an unreadable or corrupt library, in
+// whichever pass; possibly on one of the reader's threads) must not leave an unfinished database behind
+static std::string g_unfinished[2];
+
+void ku_seqio::fatal(int code, const char *fmt, ...) {
+  for (const std::string &path : g_unfinished)
+    if (!path.empty()) unlink(path.c_str());
+  va_list ap;
+  va_start(ap, fmt);
+  fprintf(stderr, "kmer_db: ");
+  vfprintf(stderr, fmt, ap);
+  fprintf(stderr, "\n");
+  va_end(ap);
+  exit(code);
+}
+using ku_seqio::fatal;
+
+static int exit_code_of(int st) {
+  switch (st) {
+    case KU_EINVAL: return EX_USAGE;
+    case KU_EDATA: return EX_DATAERR;
+    case KU_ENOINPUT: return EX_NOINPUT;
+    case KU_ENOMEM: return EX_OSERR;
+    default: return EX_SOFTWARE;
+  }
+}
+
+static void usage(int code) {
+  fprintf(stderr,
+          "Usage: kmer_db [-k 31] -n NT -o database.kdb -i database.idx [-P passes] [-s device_bytes(K/M/G)] [-t threads] [-v]\n"
+          "               library.fa [more.fa ...]\n\n"
+          "Options: (*mandatory)\n"
+          "* -n #             Length of the minimizer bin keys (1..15)\n"
+          "* -o filename      Output database (sorted, values 0: what db_sort -z writes)\n"
+          "* -i filename      Output index\n"
+          "  -k #             K-mer length (default 31; at most 31, at least -n)\n"
+          "  -P #             Passes over the input, each building a range of the bins (default 1; files only, no stdin)\n"
+          "  -s #[K|M|G]      Device memory for collecting the k-mers (default: half of what is free)\n"
+          "  -t #             Number of threads (accepted; the input stage sizes its own teams)\n"
+          "  -v               Verbose output: per pass the windows, candidates, flushes and distinct k-mers\n"
+          "  -h               Print this message\n\n"
+          "Input: FASTA, plain or .gz / .bz2; '-' or no file reads standard input.  KU_DEVICE selects the GPU.\n");
+  exit(code);
+}
+
+static bool parse_bytes(const char *txt, uint64_t &out) {
+  char *end = nullptr;
+  const unsigned long long v = strtoull(txt, &end, 10);
+  if (end == txt || *txt == '-') return false;
+  uint64_t mul = 1;
+  if (*end == 'K' || *end == 'k') mul = 1ull << 10, ++end;
+  else if (*end == 'M' || *end == 'm') mul = 1ull << 20, ++end;
+  else if (*end == 'G' || *end == 'g') mul = 1ull << 30, ++end;
+  if (*end) return false;
+  out = v * mul;
+  return true;
+}
+
+int main(int argc, char **argv) {
+  std::string kdb_name, idx_name;
+  long long k = 31, nt = 0, passes = 1;
+  uint64_t device_bytes = 0;
+  bool verbose = false;
+  if (argc < 2) usage(EX_USAGE);
+  int opt;
+  while ((opt = getopt(argc, argv, "k:n:o:i:P:s:t:vh")) != -1) {
+    switch (opt) {
+      case 'k': k = atoll(optarg); break;
+      case 'n': nt = atoll(optarg); break;
+      case 'o': kdb_name = optarg; break;
+      case 'i': idx_name = optarg; break;
+      case 'P': passes = atoll(optarg); break;
+      case 's':
+        if (!parse_bytes(optarg, device_bytes) || device_bytes == 0) fatal(EX_USAGE, "-s takes a positive size, such as 512M or 8G");
+        break;
+      case 't': if (atoll(optarg) <= 0) fatal(EX_USAGE, "can't use nonpositive thread count"); break;
+      case 'v': verbose = true; break;
+      case 'h': usage(0); break;
+      default: usage(EX_USAGE);
+    }
+  }
+  if (kdb_name.empty() || idx_name.empty() || nt == 0) usage(EX_USAGE);
+  if (nt < 1 || nt > 15) fatal(EX_USAGE, "bin key length out of range (-n 1..15)");
+  if (k < nt || k > 31) fatal(EX_USAGE, "k-mer length out of range (-k %lld..31)", nt);
+  if (passes < 1 || passes > (1ll << (2 * nt))) fatal(EX_USAGE, "-P out of range (1..4^nt)");
+  std::vector<std::string> inputs;
+  bool from_stdin = optind >= argc;
+  for (int i = optind; i < argc; ++i) {
+    if (strcmp(argv[i], "-") == 0) from_stdin = true;
+    else inputs.push_back(argv[i]);
+  }
+  if (from_stdin && !inputs.empty()) fatal(EX_USAGE, "standard input cannot be combined with files");
+  if (from_stdin && passes > 1) fatal(EX_USAGE, "-P %lld needs files: the input is read once per pass, standard input can be read only once", passes);
+  if (from_stdin) inputs.push_back("/dev/stdin");
+
+  // the outputs are created (and whatever was at their paths truncated) when the handle opens: not for an input that is not there
+  for (const std::string &path : inputs)
+    if (access(path.c_str(), R_OK) != 0) fatal(EX_NOINPUT, "can't open %s", path.c_str());
+
+  ku_kmerdb *h = nullptr;
+  const char *dev_env = getenv("KU_DEVICE");
+  int st = ku_kmerdb_open(dev_env ? atoi(dev_env) : 0, (uint32_t)k, (uint32_t)nt, (uint32_t)passes, device_bytes, kdb_name.c_str(),
+                          idx_name.c_str(), &h);
+  if (st != KU_OK) fatal(exit_code_of(st), "%s", ku_last_error());
+  g_unfinished[0] = kdb_name;
+  g_unfinished[1] = idx_name;
+  auto check = [&](int status) {
+    if (status == KU_OK) return;
+    const std::string msg = ku_last_error();
+    ku_kmerdb_close(h);  // removes the unfinished files
+    fatal(exit_code_of(status), "%s", msg.c_str());
+  };
+  ku_kmerdb_stats stats{};
+  for (long long p = 0; p < passes; ++p) {
+    uint64_t n_records = 0;
+    for (const std::string &path : inputs) {
+      ku_seqio::FastaRecords fa(path);
+      std::string id;
+      const char *seq;
+      size_t len;
+      while (fa.next(id, seq, len)) {
+        check(ku_kmerdb_add(h, seq, len));
+        ++n_records;
+      }
+    }
+    check(ku_kmerdb_end_pass(h));
+    check(ku_kmerdb_get_stats(h, &stats));
+    if (verbose)
+      fprintf(stderr, "kmer_db: pass %lld/%lld: %llu records, %llu windows, %llu candidates, %llu flushes, %llu merge calls, %llu segments, %llu distinct k-mers\n",
+              p + 1, passes, (unsigned long long)n_records, (unsigned long long)stats.windows, (unsigned long long)stats.candidates,
+              (unsigned long long)stats.flushes, (unsigned long long)stats.merge_calls, (unsigned long long)stats.segments,
+              (unsigned long long)stats.distinct);
+  }
+  uint64_t key_ct = 0;
+  check(ku_kmerdb_finish(h, &key_ct));
+  g_unfinished[0].clear();  // a database now
+  g_unfinished[1].clear();
+  check(ku_kmerdb_get_stats(h, &stats));
+  ku_kmerdb_close(h);
+  if (verbose)
+    fprintf(stderr, "kmer_db: %llu distinct k-mers in all (buffer of %llu k-mers, segments of %llu bytes); scan %.3f s, sort and merge %.3f s, "
+                    "bin order and output %.3f s\n",
+            (unsigned long long)key_ct, (unsigned long long)stats.capacity, (unsigned long long)stats.segment_bytes, stats.scan_s,
+            stats.flush_s, stats.end_pass_s);
+  return 0;
+}

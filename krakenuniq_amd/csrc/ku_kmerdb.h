@@ -1,0 +1,113 @@
+// ku_kmerdb.h -- device code of the k-mer set builder (ku_kmerdb_*, bin/kmer_db; entry points in ku_dbsort.hip): the
+// minimizer bin key shared with db_sort's second half, and the extraction kernel that turns sequence bytes into
+// canonical, unambiguous k-mers (the step the reference leaves to Jellyfish 1, scripts/build_db.sh:140-146).
+#pragma once
+#include "ku_device.h"
+
+// bin key of a canonical k-mer (KrakenDB::bin_key(kmer, nt), src/krakendb.cpp:182-215): the minimum over its k - nt + 1
+// m-mers of the scrambled canonical m-mer
+__device__ __forceinline__ uint32_t ku_bin_key(uint64_t canon, uint32_t k, uint32_t nt, uint32_t xor_mask) {
+  const uint32_t w = k - nt + 1, mask = (uint32_t)((1ull << (2 * nt)) - 1);
+  uint32_t best = 0xFFFFFFFFu;
+  for (uint32_t j = 0; j < w; ++j) {
+    const uint32_t mm = (uint32_t)(canon >> (2 * j)) & mask;
+    const uint32_t rc = ku_revcomp32(mm, nt);
+    const uint32_t v = (mm < rc ? mm : rc) ^ xor_mask;
+    best = v < best ? v : best;
+  }
+  return best;
+}
+
+// One wave scans a tile of KMD_TILE consecutive windows: its 64 lanes load 16 sequence bytes each (plus the two chunks the
+// last windows reach into), pack them to 2-bit codes and ambiguity bits in LDS, and every lane then takes 16 windows, one
+// per round, lane l of round j the window j * 64 + l of the tile -- so the 16 lanes that share a packed word read it as
+// a broadcast and the shift inside the word is the same in every round.
+#define KMD_TILE 1024
+#define KMD_ROUNDS (KMD_TILE / 64)
+#define KMD_CHUNKS (KMD_TILE / 16 + 2)  // 16-byte chunks a tile's windows cover (k <= 31: 30 bytes past the tile)
+#define KMD_WAVES 4
+
+struct KmdScan {
+  const uint8_t *seq;          // the uploaded segment, 16-byte aligned
+  uint64_t seq_bytes;          // bytes that may be loaded (a multiple of 16); the windows below lie inside it
+  uint64_t w_lo, w_hi;         // windows [w_lo, w_hi) of the segment: window w = bytes [w, w + k)
+  uint32_t k, nt, xor_mask;
+  uint32_t bin_lo, bin_hi;     // pass mode: keep the k-mers whose bin key lies in [bin_lo, bin_hi)
+  uint32_t pass_mode;          // 0: one pass, the bin key is not computed
+  uint64_t *out;               // the collection buffer
+  uint64_t cap;                // its size in k-mers; the host never launches more windows than it has room for
+  unsigned long long *cursor;  // k-mers in the buffer
+  uint32_t *err;               // set when a tile would have written past cap (a host-side accounting bug): nothing is written
+};
+
+__global__ __launch_bounds__(64 * KMD_WAVES) void kmerdb_extract_kernel(KmdScan a) {
+  __shared__ uint32_t s_code[KMD_WAVES][KMD_CHUNKS];  // 16 bases per word, the first one in bits 31..30
+  __shared__ uint32_t s_amb[KMD_WAVES][KMD_CHUNKS];   // 16 ambiguity bits per word, the first base in bit 15
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint64_t t0 = a.w_lo / KMD_TILE, t1 = (a.w_hi + KMD_TILE - 1) / KMD_TILE;
+  const uint64_t per_iter = (uint64_t)gridDim.x * KMD_WAVES;
+  const uint64_t n_iter = (t1 - t0 + per_iter - 1) / per_iter;  // the same in every block: the barriers below are uniform
+  const uint32_t sh = lane & 15, k = a.k;
+  for (uint64_t it = 0; it < n_iter; ++it) {
+    const uint64_t tile = t0 + (it * gridDim.x + blockIdx.x) * KMD_WAVES + wv;
+    const bool live = tile < t1;  // wave-uniform
+    if (live) {
+      for (uint32_t c = lane; c < KMD_CHUNKS; c += 64) {
+        const uint64_t off = tile * KMD_TILE + 16ull * c;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);  // (bytes past the segment: ambiguous, and no window below reaches them)
+        if (off + 16 <= a.seq_bytes) v = *reinterpret_cast<const uint4 *>(a.seq + off);
+        uint32_t c0, c1, c2, c3, a0, a1, a2, a3;
+        ku_pack_dword(v.x, c0, a0);
+        ku_pack_dword(v.y, c1, a1);
+        ku_pack_dword(v.z, c2, a2);
+        ku_pack_dword(v.w, c3, a3);
+        s_code[wv][c] = (c0 << 24) | (c1 << 16) | (c2 << 8) | c3;
+        s_amb[wv][c] = (a0 << 12) | (a1 << 8) | (a2 << 4) | a3;
+      }
+    }
+    __syncthreads();
+    if (live) {
+      uint64_t canon[KMD_ROUNDS];
+      uint64_t kept[KMD_ROUNDS];  // wave-uniform ballots
+      uint32_t total = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < KMD_ROUNDS; ++j) {
+        const uint32_t word = j * 4 + (lane >> 4);
+        const uint32_t w0 = s_code[wv][word], w1 = s_code[wv][word + 1], w2 = s_code[wv][word + 2];
+        // 32 bases from the window's first one on: two funnel shifts over the three words it can touch
+        const uint32_t hi = __funnelshift_l(w1, w0, 2 * sh), lo = __funnelshift_l(w2, w1, 2 * sh);
+        const uint64_t fwd = (((uint64_t)hi << 32) | lo) >> (64 - 2 * k);
+        const uint64_t amb48 = ((uint64_t)s_amb[wv][word] << 48) | ((uint64_t)s_amb[wv][word + 1] << 32) |
+                               ((uint64_t)s_amb[wv][word + 2] << 16);
+        const bool ambiguous = ((amb48 << sh) >> (64 - k)) != 0;
+        const uint64_t w = tile * KMD_TILE + j * 64 + lane;
+        bool keep = !ambiguous && w >= a.w_lo && w < a.w_hi;
+        const uint64_t rc = ku_revcomp64(fwd, k);
+        const uint64_t c = fwd < rc ? fwd : rc;
+        if (a.pass_mode && keep) {
+          const uint32_t bin = ku_bin_key(c, k, a.nt, a.xor_mask);
+          keep = bin >= a.bin_lo && bin < a.bin_hi;
+        }
+        canon[j] = c;
+        kept[j] = __ballot(keep);
+        total += (uint32_t)__popcll(kept[j]);
+      }
+      // one reservation per tile; the order inside the buffer is arbitrary, the sort fixes it
+      unsigned long long base = 0;
+      if (lane == 0 && total) base = atomicAdd(a.cursor, (unsigned long long)total);
+      base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+             (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+      if (base + total > a.cap) {
+        if (lane == 0) atomicOr(a.err, 1u);
+      } else {
+        const uint64_t below = (1ull << lane) - 1;
+#pragma unroll
+        for (uint32_t j = 0; j < KMD_ROUNDS; ++j) {
+          if ((kept[j] >> lane) & 1ull) a.out[base + (uint32_t)__popcll(kept[j] & below)] = canon[j];
+          base += (uint32_t)__popcll(kept[j]);
+        }
+      }
+    }
+    __syncthreads();  // the next tile overwrites the packed words
+  }
+}

@@ -20,6 +20,7 @@
 
 #include "../../include/krakenuniq_amd.h"
 #include "ku_seqio.h"
+#include "ku_fasta.h"
 
 void ku_seqio::fatal(int code, const char *fmt, ...) {
   va_list ap;
@@ -74,30 +75,7 @@ static void usage(int code) {
   exit(code);
 }
 
-// one FASTA record at a time through the classify executable's reader
-struct Fasta {
-  ku_seqio::Reader rd;
-  ku_seqio::Batch bt;
-  std::string header;
-  explicit Fasta(const std::string &path) {
-    bt.pinned = false;  // ku_setlcas_add takes ordinary host memory
-    rd.open(path.c_str(), /*prefetch=*/true);
-    rd.fastq = false;  // FastaReader regardless of the first byte (src/set_lcas.cpp:245,422)
-  }
-  ~Fasta() { bt.release(); }
-  bool next(std::string &id, const char *&seq, size_t &len) {
-    size_t n = 0, lo, hi;
-    bt.clear();
-    bt.begin_read();
-    if (!ku_seqio::next_record(rd, bt, &header, nullptr, &n)) return false;
-    bt.end_read();
-    ku_seqio::split_id(header.data(), header.size(), lo, hi);
-    id.assign(header, lo, hi - lo);
-    seq = bt.seqs + bt.off.back();
-    len = bt.len.back();
-    return true;
-  }
-};
+using Fasta = ku_seqio::FastaRecords;  // one FASTA record at a time (ku_fasta.h)
 
 // taxDB as set_lcas needs it: readable, extendable (-a / -A add entries) and writable (TaxonomyDB, src/taxdb.hpp)
 struct TaxTable {
