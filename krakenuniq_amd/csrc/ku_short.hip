@@ -47,6 +47,15 @@ template <int ITEMS> struct KsGeom {
   static constexpr int RCT_LOG2 = 6;                           // n_reads counter table (per wave)
 };
 
+// Four dwords of a table line at dword alignment: ONE 16-byte load that is either an entry with the dword behind it (entry i
+// lies at dword 4 + 3 i of its line; the fourth dword of entry 7 is the first SEEN word, still inside the line) or, aimed at
+// dword 0 of a line, that line's header.
+struct __attribute__((packed, aligned(4))) KsQuad {
+  uint32_t x, y, z, w;
+};
+__device__ __forceinline__ uint64_t ks_quad_key(const KsQuad &q) { return ((uint64_t)q.y << 32) | q.x; }  // as an entry: key_lo, key_hi, slot
+__device__ __forceinline__ uint4 ks_quad_header(const KsQuad &q) { return make_uint4(q.x, q.y, q.z, q.w); }
+
 // order the wave's own LDS traffic (hardware executes a wave's DS ops in order; this stops the compiler)
 __device__ __forceinline__ void ks_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -348,7 +357,8 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
   // production build has no trace of it -- the flag checks cost scalar registers and branches in the read loop):
   // 1 skip probe, 2 skip HLL, 4 skip n_kmers, 8 skip taxa store,
   // 32 skip resolve (call 0), 64 skip locus/minimizer stage (bucket 0), 128 (OUT = 2) skip the SEEN marks, 256 (OUT = 2) skip
-  // the misses' inserts into the run-wide set, 512 (OUT = 2) skip the insert counts per (unit, slot).  0 in production.
+  // the misses' inserts into the run-wide set, 512 (OUT = 2) skip the insert counts per (unit, slot), 1024 skip the probe's
+  // straggler pass (a lookup that the first entry compare leaves open stays a miss: wrong for spilled k-mers).  0 in production.
   using G = KsGeom<ITEMS>;
   constexpr uint32_t TCAP = 1u << G::TCAP_LOG2;
   __shared__ uint32_t s_codes[KS_WAVES][G::NCODES];
@@ -695,7 +705,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
         }
       }
       const uint32_t *lp[ITEMS];
-      uint32_t tag[ITEMS], cand[ITEMS];
+      uint32_t cand[ITEMS];
       bool act[ITEMS], ovf[ITEMS];
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) {
@@ -703,27 +713,37 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
         hh[j] = ku_fmix64(canon[j]);
         const uint64_t line = ku_locus_line(locus, db.n_lines);
         lp[j] = tab + (ok[j] ? line : 0) * KU_LINE_DWORDS;  // idle lanes share bucket 0 (no stray line fetches)
-        tag[j] = ku_table_tag(hh[j]);
         act[j] = ok[j] && !KS_ABL(1u);
         if (KS_ABL(64u)) lp[j] = tab;
       }
 
-      // ---- stage 4: bucket probe (header round trip, entry in the same line, lockstep tail)
-      // header loads and the first-candidate entry load are issued for every lane (inactive lanes point at
+      // ---- stage 4: bucket probe (header round trip; entry in the same line OR the following line's header; straggler pass)
+      // header loads and the second load are issued for every lane (inactive lanes point at
       // bucket 0): the instructions are issued per wave anyway, predicating them only costs exec-mask juggling
       uint4 h4[ITEMS];
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) h4[j] = *reinterpret_cast<const uint4 *>(lp[j]);
-      KuPair pr[ITEMS];
+      // What the home header says: (a) a candidate entry -- fetch it; (b) no candidate, line not spilled -- a miss, finished
+      // (fetches entry 0 for nothing: no predication); (c) no candidate, line spilled -- the lookup is certain to need the
+      // FOLLOWING line's header, and asks for it here, in the slot of the entry load, instead of one round trip later: the chain
+      // header -> entry -> next header -> entry becomes header -> [entry | next header] -> entry.  Nothing speculative: every
+      // such line was fetched before, only later.  One 16-byte load per item serves both (KsQuad).
+      KsQuad q[ITEMS];
       const uint32_t *ep[ITEMS];
+      bool nxt[ITEMS];  // (c): q[j] is the header of the line behind lp[j]
+      const uint32_t *const tab_end = tab + db.n_lines * KU_LINE_DWORDS;
 #pragma unroll
-      for (int j = 0; j < ITEMS; ++j) {  // no branch between the header wait and the entry loads of all items
-        cand[j] = ku_tag_matches(h4[j], tag[j]) & (act[j] ? 0xFFu : 0u);
+      for (int j = 0; j < ITEMS; ++j) {  // no branch between the header wait and the second loads of all items
+        cand[j] = ku_tag_matches(h4[j], ku_table_tag(hh[j])) & (act[j] ? 0xFFu : 0u);
         ovf[j] = act[j] && ku_line_spilled(h4[j]);
-        ep[j] = lp[j] + KU_LINE_ENTRY0 + 3 * (__builtin_ctz(cand[j] | 0x100u) & 7u);  // no candidate: entry 0 (bit 8 -> 0)
+        nxt[j] = ovf[j] && cand[j] == 0;
+        // dword offset from the line: the first candidate entry (no candidate: entry 0, bit 8 -> 0), or the following line
+        const uint32_t eo = nxt[j] ? (uint32_t)KU_LINE_DWORDS : KU_LINE_ENTRY0 + 3 * (__builtin_ctz(cand[j] | 0x100u) & 7u);
+        ep[j] = lp[j] + eo;
+        if (ep[j] == tab_end) ep[j] = tab;  // behind the last line comes the first (only a header address can get there)
       }
 #pragma unroll
-      for (int j = 0; j < ITEMS; ++j) pr[j] = *reinterpret_cast<const KuPair *>(ep[j]);
+      for (int j = 0; j < ITEMS; ++j) q[j] = *reinterpret_cast<const KsQuad *>(ep[j]);
       // OUT == 2 (sparse-sketch emulation): the line's SEEN bytes, one per entry (ku_device.h), come with the entry -- same
       // line, same round trip.  A k-mer the database holds is "inserted into its taxon's sparse sketch" by setting the byte of
       // its entry: a plain byte store, and only the first time (a stale 0 from this CU's L1 costs a second store, never a
@@ -736,51 +756,73 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
       }
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) {
-        const bool hit = cand[j] != 0 && (((uint64_t)pr[j].key_hi << 32) | pr[j].key_lo) == canon[j];
-        v[j] = hit ? pr[j].slot : 0u;
+        const bool hit = cand[j] != 0 && ks_quad_key(q[j]) == canon[j];
+        v[j] = hit ? q[j].z : 0u;
         if (OUT == 2 && DO_COUNTS) {
           if (hit && !sb[j] && !KS_ABL(128u)) ku_seen_mark(lp[j], (uint32_t)__builtin_ctz(cand[j]));
         }
         cand[j] &= cand[j] - 1;  // no-op for 0
-        act[j] = !hit && (cand[j] != 0 || ovf[j]);
+        act[j] = !hit && (cand[j] != 0 || ovf[j]);  // pending: candidates left, or the chain goes on ((c): its header is here)
       }
+      // Straggler pass.  At load 0.2 one lookup in 120 is still open here -- and two waves in three hold such a lane, typically
+      // ONE.  Each lane with a pending item moves its lowest one into one set of state and walks it to the end on its own: the
+      // tags of a fresh header, else the next candidate entry, else the following line, one 16-byte load per step, until the
+      // k-mer is found or the chain ends.  A lane with two pending items comes round twice.  (The loop this replaces stepped all
+      // ITEMS items in lockstep through both arms, four exec-masked regions per iteration whichever single lane was active.)
       bool any = false;
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) any |= act[j];
-      while (any) {
-        any = false;
-        KuPair e[ITEMS];
-        uint4 a4[ITEMS];
+      while (any && !KS_ABL(1024u)) {
+        // (what is cheap to get back from the items' own registers is not copied -- the tag from the hash, the k-mer by comparing
+        // with the picked item's -- : the ITEMS = 2 instances have no register to spare)
+        bool pick[ITEMS], taken = false, fresh = false, ov = false;
+        const uint32_t *l = tab;
+        uint32_t cm = 0;
+        uint64_t hsel = 0;
+        KsQuad hq = {0, 0, 0, 0};
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) {
-          if (act[j]) {
-            if (cand[j]) {
-              e[j] = *reinterpret_cast<const KuPair *>(lp[j] + KU_LINE_ENTRY0 + 3 * (__builtin_ctz(cand[j])));
-            } else {
-              lp[j] += KU_LINE_DWORDS;
-              if (lp[j] == tab + db.n_lines * KU_LINE_DWORDS) lp[j] = tab;
-              a4[j] = *reinterpret_cast<const uint4 *>(lp[j]);
+          pick[j] = act[j] && !taken;
+          taken |= act[j];
+          if (pick[j]) { hsel = hh[j]; l = lp[j]; cm = cand[j]; ov = ovf[j]; fresh = nxt[j]; hq = q[j]; }
+        }
+        const uint32_t t = ku_table_tag(hsel);
+        if (fresh) {  // the header fetched with the first entries: it is the line behind the home line
+          l += KU_LINE_DWORDS;
+          if (l == tab_end) l = tab;
+        }
+        for (;;) {
+          if (fresh) {
+            cm = ku_tag_matches(ks_quad_header(hq), t);
+            ov = ku_line_spilled(ks_quad_header(hq));
+          }
+          if (cm == 0 && !ov) break;  // the chain ends here: a miss
+          fresh = cm == 0;
+          if (fresh) {
+            l += KU_LINE_DWORDS;
+            if (l == tab_end) l = tab;
+          }
+          const uint32_t ei = (uint32_t)__builtin_ctz(cm | 0x100u) & 7u;
+          hq = *reinterpret_cast<const KsQuad *>(fresh ? l : l + KU_LINE_ENTRY0 + 3 * ei);
+          if (!fresh) {
+            cm &= cm - 1;
+            bool same = false;
+#pragma unroll
+            for (int j = 0; j < ITEMS; ++j) same |= pick[j] && ks_quad_key(hq) == canon[j];
+            if (same) {
+#pragma unroll
+              for (int j = 0; j < ITEMS; ++j)
+                if (pick[j]) v[j] = hq.z;
+              if (OUT == 2 && DO_COUNTS && !KS_ABL(128u)) ku_seen_mark(l, ei);  // (rare path: marked without a look)
+              break;
             }
           }
         }
+        any = false;
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) {
-          if (act[j]) {
-            if (cand[j]) {
-              const uint32_t ei = (uint32_t)__builtin_ctz(cand[j]);
-              cand[j] &= cand[j] - 1;
-              if ((((uint64_t)e[j].key_hi << 32) | e[j].key_lo) == canon[j]) {
-                v[j] = e[j].slot;
-                act[j] = false;
-                if (OUT == 2 && DO_COUNTS && !KS_ABL(128u)) ku_seen_mark(lp[j], ei);  // (rare path: marked without a look)
-              }
-            } else {
-              cand[j] = ku_tag_matches(a4[j], tag[j]);
-              ovf[j] = ku_line_spilled(a4[j]);
-            }
-            if (act[j]) act[j] = cand[j] != 0 || ovf[j];
-            any |= act[j];
-          }
+          if (pick[j]) act[j] = false;
+          any |= act[j];
         }
       }
 
