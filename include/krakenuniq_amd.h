@@ -138,6 +138,48 @@ int ku_kmerdb_finish(ku_kmerdb *h, uint64_t *key_ct);
 int ku_kmerdb_get_stats(const ku_kmerdb *h, ku_kmerdb_stats *out);
 void ku_kmerdb_close(ku_kmerdb *h);
 
+/* HyperLogLog sketches of a library's k-mers on the device: the reference's count_unique (src/count_unique.cpp, called by
+ * scripts/build_db.sh:127 to size the Jellyfish hash), and the per-range estimates from which kmer_db -P auto plans its passes.
+ *
+ * Every window of k bytes made of ACGTacgt only (lower case equals upper case; windows never span two records) contributes
+ * one value: its forward k-mer -- what count_unique hashes (src/count_unique.cpp:70-73: no canonical_representation) -- or,
+ * with KU_SKETCH_CANONICAL, its canonical one.  h = murmurhash3_finalizer(value) (hyperloglogplus.cpp:830, it adds 1 first),
+ * register index = the top p bits of h, rank = getRank (:140) of the rest, saturating at 64 - p + 1;
+ * registers[(group << p) + index] = max(..., rank), one byte each.  group = 0, or with n_groups > 1 the range of the k-mer's
+ * minimizer bin key: bin_key(canonical, nt) * n_groups >> 2 nt, which for a power-of-two pass count P <= n_groups puts the
+ * groups [i * n_groups / P, (i + 1) * n_groups / P) into pass i of ku_kmerdb_open exactly.  n_observed counts the windows kept,
+ * duplicates included.  The registers are always dense (the reference's final counter is: every 50 000-base piece has a dense
+ * counter, and the first merge copies it, hyperloglogplus.cpp:635-640), so ku_sketch_estimate = min(n_observed,
+ * ertlCardinality(registers)) (:722-753) is the number count_unique prints.
+ *
+ * k 1..31; p 4..18; n_groups 1, or a power of two <= min(1024, 4^nt) with nt 1..15, nt <= k (then KU_SKETCH_CANONICAL is
+ * required: the bin key is defined on canonical k-mers; nt is not looked at when n_groups is 1); segment_bytes: one upload
+ * segment (0: 64 MiB; rounded down to 1 KiB, at least 1 KiB).  ku_sketch_add takes one FASTA record, line breaks removed, and
+ * packs it into one of two pinned staging segments behind one separator byte; a segment is uploaded and scanned when it is
+ * full, the host packs the other one meanwhile.  A record longer than the room left is cut with k - 1 bytes of overlap.
+ * ku_sketch_add_values hashes the values as they are (n_groups == 1 only; each counts as one observation).  ku_sketch_export
+ * and ku_sketch_estimate scan what is staged first; they may be called repeatedly and between adds (registers and n_observed
+ * may each be null).  KU_EINVAL: bad arguments (checked before any device is touched), ku_sketch_estimate or
+ * ku_sketch_add_values with n_groups > 1, any call after one that failed; KU_EHIP: no device. */
+#define KU_SKETCH_CANONICAL 0x1u
+typedef struct ku_sketch ku_sketch;
+int ku_sketch_open(int device, uint32_t k, uint32_t p, uint32_t flags, uint32_t nt, uint32_t n_groups,
+                   uint64_t segment_bytes, ku_sketch **out);
+int ku_sketch_add(ku_sketch *h, const char *seq, uint64_t len);
+int ku_sketch_add_values(ku_sketch *h, const uint64_t *values, uint64_t n);
+int ku_sketch_export(ku_sketch *h, uint8_t *registers /* [n_groups << p] */, uint64_t *n_observed);
+int ku_sketch_estimate(ku_sketch *h, uint64_t *estimate);
+void ku_sketch_close(ku_sketch *h);
+/* Host only: the smallest power of two P <= n_groups (itself a power of two, 1..1024) such that for every pass i the Ertl
+ * estimate (not clipped to an observation count) of the max-merge of the groups [i * n_groups / P, (i + 1) * n_groups / P)
+ * satisfies  estimate * 11 <= usable_kmers * 10.  The margin is derived, not measured: at p = 12 the estimate's relative
+ * standard error is 1.04 / sqrt(4096), about 1.6 %, and 10 % is six of those; the integer form is there so that the rule
+ * can be restated without floating point.  *fullest_estimate (may be null): the largest estimate among the passes of the P
+ * returned.  KU_ENOMEM when P = n_groups does not fit either (*n_passes = n_groups, *fullest_estimate that of its fullest
+ * group); KU_EINVAL for bad arguments. */
+int ku_sketch_plan_passes(const uint8_t *registers, uint32_t n_groups, uint32_t p, uint64_t usable_kmers,
+                          uint32_t *n_passes, uint64_t *fullest_estimate);
+
 /* ------------------------------------------------------------------ taxonomy
  * Host taxonomy: taxDB text -> entries + Parent_map
  * (taxdb.hpp:563-605 readTaxonomyIndex_, :411-433 createPointers, :383-398 getParentMap). */

@@ -99,6 +99,13 @@ SIGNATURES = {
     "ku_kmerdb_finish": (C.c_int, [C.c_void_p, u64p]),
     "ku_kmerdb_get_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ku_kmerdb_close": (None, [C.c_void_p]),
+    "ku_sketch_open": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "ku_sketch_add": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "ku_sketch_add_values": (C.c_int, [C.c_void_p, u64p, C.c_uint64]),
+    "ku_sketch_export": (C.c_int, [C.c_void_p, u8p, u64p]),
+    "ku_sketch_estimate": (C.c_int, [C.c_void_p, u64p]),
+    "ku_sketch_close": (None, [C.c_void_p]),
+    "ku_sketch_plan_passes": (C.c_int, [u8p, C.c_uint32, C.c_uint32, C.c_uint64, u32p, u64p]),
     "ku_ctx_swap_shard": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "ku_ctx_prefetch_shard": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "ku_ctx_mem_info": (C.c_int, [C.c_void_p, u64p, u64p]),
@@ -928,6 +935,71 @@ def kmer_db_files(fasta_seqs, out_kdb, out_idx, k, nt, passes=1, device_bytes=0,
                 b.add(s)
             per_pass.append(b.end_pass())
         return b.finish(), per_pass
+
+
+KU_SKETCH_CANONICAL = 1
+
+
+class Sketch:
+    """HyperLogLog sketches of a library's k-mers on the device (ku_sketch_*): one of the forward k-mers (count_unique), or with
+    flags=KU_SKETCH_CANONICAL of the canonical ones, then also one per range of the minimizer bin keys (n_groups > 1)
+
+        with Sketch(k, p) as s:
+            for rec in seqs: s.add(rec)
+            n = s.estimate()
+    """
+
+    def __init__(self, k, p=14, flags=0, nt=0, n_groups=1, segment_bytes=0, device=0):
+        self.h = C.c_void_p()
+        self.p, self.n_groups = p, n_groups
+        _chk(lib().ku_sketch_open(device, k, p, flags, nt, n_groups, segment_bytes, C.byref(self.h)), "ku_sketch_open")
+
+    def add(self, seq: bytes):
+        _chk(lib().ku_sketch_add(self.h, seq, len(seq)), "ku_sketch_add")
+
+    def add_values(self, values):
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        _chk(lib().ku_sketch_add_values(self.h, _p(v, u64p), len(v)), "ku_sketch_add_values")
+
+    def export(self):
+        """(registers [n_groups, 2^p] uint8, n_observed)"""
+        regs = np.zeros((self.n_groups, 1 << self.p), dtype=np.uint8)
+        n = C.c_uint64()
+        _chk(lib().ku_sketch_export(self.h, _p(regs, u8p), C.byref(n)), "ku_sketch_export")
+        return regs, n.value
+
+    def estimate(self):
+        n = C.c_uint64()
+        _chk(lib().ku_sketch_estimate(self.h, C.byref(n)), "ku_sketch_estimate")
+        return n.value
+
+    def close(self):
+        if self.h:
+            lib().ku_sketch_close(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sketch_plan_passes(registers, usable):
+    """registers [n_groups, 2^p] -> (passes, fullest estimate): the smallest power-of-two pass count whose fullest pass fits
+    `usable` k-mers with a tenth to spare (ku_sketch_plan_passes); KuError -4 when none does"""
+    r = np.ascontiguousarray(registers, dtype=np.uint8)
+    assert r.ndim == 2 and r.shape[1] & (r.shape[1] - 1) == 0
+    n, full = C.c_uint32(), C.c_uint64()
+    _chk(lib().ku_sketch_plan_passes(_p(r, u8p), r.shape[0], r.shape[1].bit_length() - 1, int(usable), C.byref(n), C.byref(full)),
+         "ku_sketch_plan_passes")
+    return n.value, full.value
 
 
 def hll_cardinality(registers, n_observed, p=12):

@@ -1,11 +1,13 @@
 // kmer_db: library FASTA -> sorted database.kdb + database.idx on the GPU through ku_kmerdb_*.  It stands where the
 // reference's build runs Jellyfish 1 and db_sort (scripts/build_db.sh:140-146 and :201): no k-mer list is written in
 // between, the values are 0 as after db_sort -z, and set_lcas follows as before.  The input goes through the same stage as
-// set_lcas's -F file (plain, .gz / BGZF, .bz2); with -P above 1 it is read once per pass.
+// set_lcas's -F file (plain, .gz / BGZF, .bz2); with -P above 1 it is read once per pass.  -P auto reads it once more,
+// beforehand: one HyperLogLog sketch per range of the bin keys (ku_sketch_*) tells the smallest pass count that fits the budget.
 #include <getopt.h>
 #include <sysexits.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -53,7 +55,8 @@ static void usage(int code) {
           "* -o filename      Output database (sorted, values 0: what db_sort -z writes)\n"
           "* -i filename      Output index\n"
           "  -k #             K-mer length (default 31; at most 31, at least -n)\n"
-          "  -P #             Passes over the input, each building a range of the bins (default 1; files only, no stdin)\n"
+          "  -P #|auto        Passes over the input, each building a range of the bins (default 1; files only, no stdin).\n"
+          "                   auto: the smallest power of two that fits -s, found by sketching the library first\n"
           "  -s #[K|M|G]      Device memory for collecting the k-mers (default: half of what is free)\n"
           "  -t #             Number of threads (accepted; the input stage sizes its own teams)\n"
           "  -v               Verbose output: per pass the windows, candidates, flushes and distinct k-mers\n"
@@ -75,11 +78,63 @@ static bool parse_bytes(const char *txt, uint64_t &out) {
   return true;
 }
 
+// -P auto: one sketch of the canonical k-mers per range of the bin keys (min(1024, 4^nt) ranges, p = 12), taken in a pass of its
+// own and closed before the builder measures the free memory; then the smallest power-of-two pass count whose fullest pass
+// fits the collection buffer of the budget with a tenth to spare (ku_sketch_plan_passes).  Without -s the budget is half of
+// what is free when the builder opens: a handle opened for the purpose reports the capacity it got, and the build then asks
+// for that budget by its size.
+static long long plan_passes(int device, uint32_t k, uint32_t nt, const std::vector<std::string> &inputs,
+                             const std::string &kdb_name, const std::string &idx_name, uint64_t &device_bytes, bool verbose) {
+  const uint32_t p = 12, n_groups = (uint32_t)std::min<uint64_t>(1024, 1ull << (2 * nt));
+  if (device_bytes && device_bytes < KU_KMERDB_MIN_BYTES) fatal(EX_USAGE, "the device budget is below the minimum of 64 KiB");
+  ku_sketch *sk = nullptr;
+  int st = ku_sketch_open(device, k, p, KU_SKETCH_CANONICAL, nt, n_groups, 0, &sk);
+  if (st != KU_OK) fatal(exit_code_of(st), "%s", ku_last_error());
+  auto check = [&](int status) {
+    if (status == KU_OK) return;
+    const std::string msg = ku_last_error();
+    ku_sketch_close(sk);
+    fatal(exit_code_of(status), "%s", msg.c_str());
+  };
+  for (const std::string &path : inputs) {
+    ku_seqio::FastaRecords fa(path);
+    std::string id;
+    const char *seq;
+    size_t len;
+    while (fa.next(id, seq, len)) check(ku_sketch_add(sk, seq, len));
+  }
+  std::vector<uint8_t> registers((size_t)n_groups << p);
+  check(ku_sketch_export(sk, registers.data(), nullptr));
+  ku_sketch_close(sk);
+  if (device_bytes == 0) {
+    ku_kmerdb *probe = nullptr;
+    ku_kmerdb_stats got{};
+    st = ku_kmerdb_open(device, k, nt, 1, 0, kdb_name.c_str(), idx_name.c_str(), &probe);
+    if (st == KU_OK) st = ku_kmerdb_get_stats(probe, &got);
+    const std::string msg = st == KU_OK ? "" : ku_last_error();
+    ku_kmerdb_close(probe);  // (removes the two empty files again)
+    if (st != KU_OK) fatal(exit_code_of(st), "%s", msg.c_str());
+    device_bytes = got.capacity * 16 + got.segment_bytes;
+  }
+  // the budget rule of ku_kmerdb_open; 1/64 of the buffer has to stay free
+  const uint64_t segment = std::min<uint64_t>((uint64_t)64 << 20, device_bytes / 64) & ~(uint64_t)1023;
+  const uint64_t capacity = (device_bytes - segment) / 16, usable = capacity - capacity / 64;
+  uint32_t n_passes = 0;
+  uint64_t fullest = 0;
+  st = ku_sketch_plan_passes(registers.data(), n_groups, p, usable, &n_passes, &fullest);
+  if (st != KU_OK)
+    fatal(EX_SOFTWARE, "no pass count up to %u fits the device budget: %s (a larger -s)", n_groups, ku_last_error());
+  if (verbose)
+    fprintf(stderr, "kmer_db: planned passes: %u (fullest range ≈ %llu k-mers of %llu)\n", n_passes, (unsigned long long)fullest,
+            (unsigned long long)usable);
+  return n_passes;
+}
+
 int main(int argc, char **argv) {
   std::string kdb_name, idx_name;
   long long k = 31, nt = 0, passes = 1;
   uint64_t device_bytes = 0;
-  bool verbose = false;
+  bool verbose = false, auto_passes = false;
   if (argc < 2) usage(EX_USAGE);
   int opt;
   while ((opt = getopt(argc, argv, "k:n:o:i:P:s:t:vh")) != -1) {
@@ -88,7 +143,10 @@ int main(int argc, char **argv) {
       case 'n': nt = atoll(optarg); break;
       case 'o': kdb_name = optarg; break;
       case 'i': idx_name = optarg; break;
-      case 'P': passes = atoll(optarg); break;
+      case 'P':
+        auto_passes = strcmp(optarg, "auto") == 0;
+        passes = auto_passes ? 1 : atoll(optarg);
+        break;
       case 's':
         if (!parse_bytes(optarg, device_bytes) || device_bytes == 0) fatal(EX_USAGE, "-s takes a positive size, such as 512M or 8G");
         break;
@@ -109,6 +167,7 @@ int main(int argc, char **argv) {
     else inputs.push_back(argv[i]);
   }
   if (from_stdin && !inputs.empty()) fatal(EX_USAGE, "standard input cannot be combined with files");
+  if (from_stdin && auto_passes) fatal(EX_USAGE, "-P auto needs files: the input is read once per pass, standard input can be read only once");
   if (from_stdin && passes > 1) fatal(EX_USAGE, "-P %lld needs files: the input is read once per pass, standard input can be read only once", passes);
   if (from_stdin) inputs.push_back("/dev/stdin");
 
@@ -116,9 +175,12 @@ int main(int argc, char **argv) {
   for (const std::string &path : inputs)
     if (access(path.c_str(), R_OK) != 0) fatal(EX_NOINPUT, "can't open %s", path.c_str());
 
-  ku_kmerdb *h = nullptr;
   const char *dev_env = getenv("KU_DEVICE");
-  int st = ku_kmerdb_open(dev_env ? atoi(dev_env) : 0, (uint32_t)k, (uint32_t)nt, (uint32_t)passes, device_bytes, kdb_name.c_str(),
+  const int device = dev_env ? atoi(dev_env) : 0;
+  if (auto_passes) passes = plan_passes(device, (uint32_t)k, (uint32_t)nt, inputs, kdb_name, idx_name, device_bytes, verbose);
+
+  ku_kmerdb *h = nullptr;
+  int st = ku_kmerdb_open(device, (uint32_t)k, (uint32_t)nt, (uint32_t)passes, device_bytes, kdb_name.c_str(),
                           idx_name.c_str(), &h);
   if (st != KU_OK) fatal(exit_code_of(st), "%s", ku_last_error());
   g_unfinished[0] = kdb_name;

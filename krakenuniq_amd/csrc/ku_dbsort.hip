@@ -25,6 +25,7 @@
 #include "ku_host.h"
 #include "ku_internal.h"
 #include "ku_kmerdb.h"
+#include "ku_sketch.h"
 
 namespace {
 
@@ -260,7 +261,8 @@ extern "C" int ku_db_sort_files(int device, const char *in_path, const char *out
 // k-mers, so no counts are kept: the extraction kernel (ku_kmerdb.h) appends every canonical, unambiguous k-mer of the
 // uploaded segment to a device buffer; when the next launch might not fit, the candidates are sorted, made unique and
 // merged into the pass's sorted distinct set, which lives at the front of the same buffer.  ku_kmerdb_end_pass hands the
-// set to dbsort_bin_order_and_pack and appends its records and its part of the index to the files.
+// set to dbsort_bin_order_and_pack and appends its records and its part of the index to the files.  (ku_sketch_*, at the end
+// of this file, estimates beforehand how many passes a library needs.)
 //
 // Budget rule (include/krakenuniq_amd.h): segment = min(64 MiB, device_bytes / 64) rounded down to 1 KiB, capacity =
 // (device_bytes - segment) / 16 k-mers in each of two buffers (the second is the sort's and the merge's other side).
@@ -661,5 +663,229 @@ extern "C" int ku_kmerdb_finish(ku_kmerdb *h, uint64_t *key_ct) {
   if (!ok) { ::unlink(h->kdb_path.c_str()); ::unlink(h->idx_path.c_str()); return kmd_fail(h, KU_ENOINPUT, "write error on " + h->kdb_path); }
   h->finished = true;
   if (key_ct) *key_ct = h->key_ct;
+  return KU_OK;
+}
+
+// =====================================================================================================================
+// ku_sketch_*: HyperLogLog sketches of a library's k-mers (ku_sketch.h): bin/count_unique (one sketch of the forward k-mers,
+// the reference's count_unique) and kmer_db -P auto (one sketch of the canonical k-mers per range of the bin keys).
+//
+// ku_sketch_add packs the records into one of two pinned staging segments, one non-ACGT byte between two of them -- a window
+// across two records holds it and is dropped as ambiguous --, so a launch scans a whole segment however short the records
+// are.  A full segment is uploaded and scanned on the handle's stream and an event recorded behind it; the host goes on
+// packing into the other segment and waits for a segment's event only when it comes back to it.
+struct ku_sketch {
+  int device = 0;
+  uint32_t k = 0, p = 0, flags = 0, nt = 0, n_groups = 1;
+  uint64_t seg_bytes = 0;
+  bool failed = false;
+  hipStream_t stream = nullptr;
+  char *h_seg[2] = {nullptr, nullptr};     // pinned
+  uint8_t *d_seg[2] = {nullptr, nullptr};
+  hipEvent_t done[2] = {nullptr, nullptr};  // behind the last work that reads h_seg[i] / d_seg[i]
+  bool in_flight[2] = {false, false};
+  int cur = 0;           // the segment being packed
+  uint64_t fill = 0;     // bytes packed into it
+  uint8_t *d_reg = nullptr;
+  unsigned long long *d_obs = nullptr;
+  uint64_t values_observed = 0;  // ku_sketch_add_values counts on the host
+};
+
+namespace {
+
+constexpr uint64_t SK_MAX_GROUPS = 1024;
+constexpr char SK_SEPARATOR = 'N';
+
+int sk_fail(ku_sketch *h, int code, const std::string &msg) {
+  h->failed = true;
+  return fail(code, msg);
+}
+
+}  // namespace
+
+#define SK_HIP(expr)                                                                              \
+  do {                                                                                            \
+    hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess) return sk_fail(h, e_ == hipErrorOutOfMemory ? KU_ENOMEM : KU_EHIP,      \
+                                         std::string("sketch: ") + #expr + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// the segment being packed may be written: what read it last has finished
+static int sk_segment_ready(ku_sketch *h) {
+  if (h->in_flight[h->cur]) {
+    SK_HIP(hipEventSynchronize(h->done[h->cur]));
+    h->in_flight[h->cur] = false;
+  }
+  return KU_OK;
+}
+
+// upload the packed segment and scan its windows; the other segment is packed next
+static int sk_scan_segment(ku_sketch *h) {
+  const uint64_t fill = h->fill;
+  h->fill = 0;
+  if (fill < h->k) return KU_OK;  // no window
+  const int c = h->cur;
+  hipStream_t s = h->stream;
+  SK_HIP(hipMemcpyAsync(h->d_seg[c], h->h_seg[c], fill, hipMemcpyHostToDevice, s));
+  const uint64_t INDEX2_XOR_MASK = 0xe37e28c4271b5a2dULL;  // krakendb.cpp:45 (KRAKIX2)
+  KuSketchScan a{};
+  a.seq = h->d_seg[c];
+  a.seq_bytes = h->seg_bytes;  // (bytes behind `fill` are those of an earlier segment: no window below reaches them)
+  a.w_lo = 0;
+  a.w_hi = fill - h->k + 1;
+  a.k = h->k;
+  a.p = h->p;
+  a.canonical = (h->flags & KU_SKETCH_CANONICAL) ? 1u : 0u;
+  a.nt = h->nt;
+  a.xor_mask = h->n_groups > 1 ? (uint32_t)(INDEX2_XOR_MASK & ((1ull << (2 * h->nt)) - 1)) : 0u;
+  a.n_groups = h->n_groups;
+  a.registers = h->d_reg;
+  a.n_observed = h->d_obs;
+  const uint64_t tiles = (a.w_hi + KMD_TILE - 1) / KMD_TILE;
+  const unsigned grid = (unsigned)std::min<uint64_t>((tiles + KMD_WAVES - 1) / KMD_WAVES, 2048);
+  hipLaunchKernelGGL(kmersketch_kernel, dim3(grid), dim3(64 * KMD_WAVES), 0, s, a);
+  SK_HIP(hipGetLastError());
+  SK_HIP(hipEventRecord(h->done[c], s));
+  h->in_flight[c] = true;
+  h->cur = c ^ 1;
+  return KU_OK;
+}
+
+extern "C" int ku_sketch_open(int device, uint32_t k, uint32_t p, uint32_t flags, uint32_t nt, uint32_t n_groups,
+                              uint64_t segment_bytes, ku_sketch **out) {
+  if (!out) return fail(KU_EINVAL, "ku_sketch_open: null argument");
+  *out = nullptr;
+  if (k < 1 || k > 31) return fail(KU_EINVAL, "k out of range (1..31)");
+  if (p < 4 || p > 18) return fail(KU_EINVAL, "HLL precision out of range (4..18)");
+  if (flags & ~(uint32_t)KU_SKETCH_CANONICAL) return fail(KU_EINVAL, "ku_sketch_open: unknown flag");
+  if (n_groups != 1) {
+    if (nt < 1 || nt > 15) return fail(KU_EINVAL, "bin key length out of range (1..15: 32-bit minimizers, krakendb.cpp:203)");
+    if (k < nt) return fail(KU_EINVAL, "bin key longer than the k-mers");
+    if (n_groups == 0 || (n_groups & (n_groups - 1)) || n_groups > std::min<uint64_t>(SK_MAX_GROUPS, 1ull << (2 * nt)))
+      return fail(KU_EINVAL, "the number of groups must be 1 or a power of two up to min(1024, 4^nt)");
+    if (!(flags & KU_SKETCH_CANONICAL)) return fail(KU_EINVAL, "groups need KU_SKETCH_CANONICAL: the bin key is defined on canonical k-mers");
+  }
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(KU_EHIP, "no HIP device available (this library has no CPU fallback)");
+  if (device < 0 || device >= n_dev) return fail(KU_EINVAL, "device index out of range");
+  ku_sketch *h = new ku_sketch();
+  h->device = device;
+  h->k = k;
+  h->p = p;
+  h->flags = flags;
+  h->nt = nt;
+  h->n_groups = n_groups;
+  h->seg_bytes = std::max<uint64_t>((segment_bytes ? segment_bytes : KMD_MAX_SEGMENT) & ~(uint64_t)1023, 1024);
+  const int st = [&]() -> int {
+    SK_HIP(hipSetDevice(device));
+    SK_HIP(hipStreamCreate(&h->stream));
+    for (int i = 0; i < 2; ++i) {
+      SK_HIP(hipHostMalloc((void **)&h->h_seg[i], h->seg_bytes, hipHostMallocDefault));
+      SK_HIP(hipMalloc((void **)&h->d_seg[i], h->seg_bytes));
+      SK_HIP(hipEventCreateWithFlags(&h->done[i], hipEventDisableTiming));
+    }
+    SK_HIP(hipMalloc((void **)&h->d_reg, (size_t)n_groups << p));
+    SK_HIP(hipMalloc((void **)&h->d_obs, 8));
+    SK_HIP(hipMemsetAsync(h->d_reg, 0, (size_t)n_groups << p, h->stream));
+    SK_HIP(hipMemsetAsync(h->d_obs, 0, 8, h->stream));
+    SK_HIP(hipStreamSynchronize(h->stream));
+    return KU_OK;
+  }();
+  if (st != KU_OK) { ku_sketch_close(h); return st; }
+  *out = h;
+  return KU_OK;
+}
+
+extern "C" void ku_sketch_close(ku_sketch *h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (int i = 0; i < 2; ++i) {
+    if (h->done[i]) (void)hipEventDestroy(h->done[i]);
+    if (h->d_seg[i]) (void)hipFree(h->d_seg[i]);
+    if (h->h_seg[i]) (void)hipHostFree(h->h_seg[i]);
+  }
+  if (h->d_reg) (void)hipFree(h->d_reg);
+  if (h->d_obs) (void)hipFree(h->d_obs);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+}
+
+extern "C" int ku_sketch_add(ku_sketch *h, const char *seq, uint64_t len) {
+  if (!h || (len && !seq)) return fail(KU_EINVAL, "ku_sketch_add: null argument");
+  if (h->failed) return fail(KU_EINVAL, "ku_sketch_add: an earlier call on this handle failed");
+  const uint64_t k = h->k, seg = h->seg_bytes;
+  if (len < k) return KU_OK;  // no window
+  SK_HIP(hipSetDevice(h->device));
+  // A record longer than the room left is cut with k - 1 bytes of overlap: the part packed here ends the segment, its windows
+  // are all those that start in [pos, pos + take - k], and the next part starts at the window behind them.
+  for (uint64_t pos = 0;;) {
+    const uint64_t rem = len - pos;  // >= k
+    if (seg - h->fill < k) {         // not one window's worth of room (fill > 0: a segment holds at least 1 KiB)
+      if (int st = sk_scan_segment(h)) return st;
+      continue;
+    }
+    if (h->fill == 0)
+      if (int st = sk_segment_ready(h)) return st;
+    const uint64_t take = std::min<uint64_t>(rem, seg - h->fill);
+    memcpy(h->h_seg[h->cur] + h->fill, seq + pos, take);
+    h->fill += take;
+    if (take == rem) {
+      if (h->fill < seg) h->h_seg[h->cur][h->fill++] = SK_SEPARATOR;
+      if (h->fill == seg)
+        if (int st = sk_scan_segment(h)) return st;
+      return KU_OK;
+    }
+    if (int st = sk_scan_segment(h)) return st;
+    pos += take - (k - 1);
+  }
+}
+
+extern "C" int ku_sketch_add_values(ku_sketch *h, const uint64_t *values, uint64_t n) {
+  if (!h || (n && !values)) return fail(KU_EINVAL, "ku_sketch_add_values: null argument");
+  if (h->failed) return fail(KU_EINVAL, "ku_sketch_add_values: an earlier call on this handle failed");
+  if (h->n_groups != 1) return fail(KU_EINVAL, "ku_sketch_add_values: one group only (a value has no bin key)");
+  SK_HIP(hipSetDevice(h->device));
+  if (int st = sk_scan_segment(h)) return st;  // the values travel through the staging segments too
+  const uint64_t per_seg = h->seg_bytes / 8;
+  for (uint64_t at = 0; at < n;) {
+    if (int st = sk_segment_ready(h)) return st;
+    const int c = h->cur;
+    const uint64_t take = std::min<uint64_t>(per_seg, n - at);
+    memcpy(h->h_seg[c], values + at, take * 8);
+    SK_HIP(hipMemcpyAsync(h->d_seg[c], h->h_seg[c], take * 8, hipMemcpyHostToDevice, h->stream));
+    const unsigned grid = (unsigned)std::min<uint64_t>((take + KU_SKETCH_BLOCK - 1) / KU_SKETCH_BLOCK, 2048);
+    hipLaunchKernelGGL(kmersketch_values_kernel, dim3(grid), dim3(KU_SKETCH_BLOCK), 0, h->stream,
+                       reinterpret_cast<const uint64_t *>(h->d_seg[c]), take, h->p, h->d_reg);
+    SK_HIP(hipGetLastError());
+    SK_HIP(hipEventRecord(h->done[c], h->stream));
+    h->in_flight[c] = true;
+    h->cur = c ^ 1;
+    h->values_observed += take;
+    at += take;
+  }
+  return KU_OK;
+}
+
+extern "C" int ku_sketch_export(ku_sketch *h, uint8_t *registers, uint64_t *n_observed) {
+  if (!h) return fail(KU_EINVAL, "ku_sketch_export: null argument");
+  if (h->failed) return fail(KU_EINVAL, "ku_sketch_export: an earlier call on this handle failed");
+  SK_HIP(hipSetDevice(h->device));
+  if (int st = sk_scan_segment(h)) return st;  // what is staged
+  unsigned long long obs = 0;
+  if (registers) SK_HIP(hipMemcpyAsync(registers, h->d_reg, (size_t)h->n_groups << h->p, hipMemcpyDeviceToHost, h->stream));
+  SK_HIP(hipMemcpyAsync(&obs, h->d_obs, 8, hipMemcpyDeviceToHost, h->stream));
+  SK_HIP(hipStreamSynchronize(h->stream));
+  if (n_observed) *n_observed = obs + h->values_observed;
+  return KU_OK;
+}
+
+extern "C" int ku_sketch_estimate(ku_sketch *h, uint64_t *estimate) {
+  if (!h || !estimate) return fail(KU_EINVAL, "ku_sketch_estimate: null argument");
+  if (h->n_groups != 1) return fail(KU_EINVAL, "ku_sketch_estimate: one group only (ku_sketch_export gives every group's registers)");
+  std::vector<uint8_t> regs((size_t)1 << h->p);
+  uint64_t obs = 0;
+  if (int st = ku_sketch_export(h, regs.data(), &obs)) return st;
+  *estimate = ku_hll_cardinality(regs.data(), h->p, obs);  // min(n_observed, Ertl): what the reference's count_unique prints
   return KU_OK;
 }

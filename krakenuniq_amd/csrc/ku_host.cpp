@@ -81,6 +81,36 @@ extern "C" uint64_t ku_hll_cardinality_sparse(const uint32_t *encoded, uint64_t 
   return ertl_from_histogram(C, q, double(1 << pp), n_observed);
 }
 
+// The pass planner of kmer_db -P auto (include/krakenuniq_amd.h): the sketches of the bin-key ranges a pass owns are merged
+// register by register (the sketch of a union is the maximum) and estimated without the clip to an observation count.
+extern "C" int ku_sketch_plan_passes(const uint8_t *registers, uint32_t n_groups, uint32_t p, uint64_t usable_kmers,
+                                     uint32_t *n_passes, uint64_t *fullest_estimate) {
+  if (!registers || !n_passes) { ku_set_error("ku_sketch_plan_passes: null argument"); return KU_EINVAL; }
+  if (n_groups < 1 || n_groups > 1024 || (n_groups & (n_groups - 1))) { ku_set_error("ku_sketch_plan_passes: the number of groups must be a power of two up to 1024"); return KU_EINVAL; }
+  if (p < 4 || p > 18) { ku_set_error("HLL precision out of range (4..18)"); return KU_EINVAL; }
+  const size_t m = (size_t)1 << p;
+  std::vector<uint8_t> merged(m);
+  uint64_t fullest = 0;
+  for (uint32_t P = 1;; P *= 2) {
+    const uint32_t per_pass = n_groups / P;
+    fullest = 0;
+    for (uint32_t i = 0; i < P; ++i) {
+      const uint8_t *g = registers + (size_t)i * per_pass * m;
+      std::copy(g, g + m, merged.begin());
+      for (uint32_t j = 1; j < per_pass; ++j)
+        for (size_t r = 0; r < m; ++r) merged[r] = std::max(merged[r], g[j * m + r]);
+      fullest = std::max(fullest, ku_hll_cardinality(merged.data(), p, UINT64_MAX));
+    }
+    if (fullest_estimate) *fullest_estimate = fullest;
+    *n_passes = P;
+    if ((unsigned __int128)fullest * 11 <= (unsigned __int128)usable_kmers * 10) return KU_OK;
+    if (P == n_groups) break;
+  }
+  ku_set_error("the fullest of the " + std::to_string(n_groups) + " bin-key ranges holds about " + std::to_string(fullest) +
+               " distinct k-mers, more than fit a budget of " + std::to_string(usable_kmers) + " k-mers with a tenth to spare");
+  return KU_ENOMEM;
+}
+
 // ---------------------------------------------------------------------------- UID databases (classify -I)
 struct ku_uid_map {
   std::vector<uint32_t> blocks;  // {taxid, parent uid} of uid i + 1 at 2 * i

@@ -27,6 +27,36 @@ __device__ __forceinline__ uint32_t ku_bin_key(uint64_t canon, uint32_t k, uint3
 #define KMD_CHUNKS (KMD_TILE / 16 + 2)  // 16-byte chunks a tile's windows cover (k <= 31: 30 bytes past the tile)
 #define KMD_WAVES 4
 
+// the tile's KMD_CHUNKS 16-byte chunks -> packed words of the wave's LDS rows (code: 16 bases per word, the first one in bits
+// 31..30; amb: 16 ambiguity bits per word, the first base in bit 15).  The caller puts a barrier between this and kmd_window.
+__device__ __forceinline__ void kmd_pack_tile(const uint8_t *__restrict__ seq, uint64_t seq_bytes, uint64_t tile, uint32_t lane,
+                                              uint32_t *s_code, uint32_t *s_amb) {
+  for (uint32_t c = lane; c < KMD_CHUNKS; c += 64) {
+    const uint64_t off = tile * KMD_TILE + 16ull * c;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);  // (bytes past the segment: ambiguous, and no window below reaches them)
+    if (off + 16 <= seq_bytes) v = *reinterpret_cast<const uint4 *>(seq + off);
+    uint32_t c0, c1, c2, c3, a0, a1, a2, a3;
+    ku_pack_dword(v.x, c0, a0);
+    ku_pack_dword(v.y, c1, a1);
+    ku_pack_dword(v.z, c2, a2);
+    ku_pack_dword(v.w, c3, a3);
+    s_code[c] = (c0 << 24) | (c1 << 16) | (c2 << 8) | c3;
+    s_amb[c] = (a0 << 12) | (a1 << 8) | (a2 << 4) | a3;
+  }
+}
+
+// window j * 64 + lane of the packed tile: its forward k-mer; true when one of its k bytes is ambiguous
+__device__ __forceinline__ bool kmd_window(const uint32_t *s_code, const uint32_t *s_amb, uint32_t j, uint32_t lane, uint32_t k,
+                                           uint64_t &fwd) {
+  const uint32_t word = j * 4 + (lane >> 4), sh = lane & 15;
+  const uint32_t w0 = s_code[word], w1 = s_code[word + 1], w2 = s_code[word + 2];
+  // 32 bases from the window's first one on: two funnel shifts over the three words it can touch
+  const uint32_t hi = __funnelshift_l(w1, w0, 2 * sh), lo = __funnelshift_l(w2, w1, 2 * sh);
+  fwd = (((uint64_t)hi << 32) | lo) >> (64 - 2 * k);
+  const uint64_t amb48 = ((uint64_t)s_amb[word] << 48) | ((uint64_t)s_amb[word + 1] << 32) | ((uint64_t)s_amb[word + 2] << 16);
+  return ((amb48 << sh) >> (64 - k)) != 0;
+}
+
 struct KmdScan {
   const uint8_t *seq;          // the uploaded segment, 16-byte aligned
   uint64_t seq_bytes;          // bytes that may be loaded (a multiple of 16); the windows below lie inside it
@@ -47,23 +77,12 @@ __global__ __launch_bounds__(64 * KMD_WAVES) void kmerdb_extract_kernel(KmdScan 
   const uint64_t t0 = a.w_lo / KMD_TILE, t1 = (a.w_hi + KMD_TILE - 1) / KMD_TILE;
   const uint64_t per_iter = (uint64_t)gridDim.x * KMD_WAVES;
   const uint64_t n_iter = (t1 - t0 + per_iter - 1) / per_iter;  // the same in every block: the barriers below are uniform
-  const uint32_t sh = lane & 15, k = a.k;
+  const uint32_t k = a.k;
   for (uint64_t it = 0; it < n_iter; ++it) {
     const uint64_t tile = t0 + (it * gridDim.x + blockIdx.x) * KMD_WAVES + wv;
     const bool live = tile < t1;  // wave-uniform
     if (live) {
-      for (uint32_t c = lane; c < KMD_CHUNKS; c += 64) {
-        const uint64_t off = tile * KMD_TILE + 16ull * c;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);  // (bytes past the segment: ambiguous, and no window below reaches them)
-        if (off + 16 <= a.seq_bytes) v = *reinterpret_cast<const uint4 *>(a.seq + off);
-        uint32_t c0, c1, c2, c3, a0, a1, a2, a3;
-        ku_pack_dword(v.x, c0, a0);
-        ku_pack_dword(v.y, c1, a1);
-        ku_pack_dword(v.z, c2, a2);
-        ku_pack_dword(v.w, c3, a3);
-        s_code[wv][c] = (c0 << 24) | (c1 << 16) | (c2 << 8) | c3;
-        s_amb[wv][c] = (a0 << 12) | (a1 << 8) | (a2 << 4) | a3;
-      }
+      kmd_pack_tile(a.seq, a.seq_bytes, tile, lane, s_code[wv], s_amb[wv]);
     }
     __syncthreads();
     if (live) {
@@ -72,14 +91,8 @@ __global__ __launch_bounds__(64 * KMD_WAVES) void kmerdb_extract_kernel(KmdScan 
       uint32_t total = 0;
 #pragma unroll
       for (uint32_t j = 0; j < KMD_ROUNDS; ++j) {
-        const uint32_t word = j * 4 + (lane >> 4);
-        const uint32_t w0 = s_code[wv][word], w1 = s_code[wv][word + 1], w2 = s_code[wv][word + 2];
-        // 32 bases from the window's first one on: two funnel shifts over the three words it can touch
-        const uint32_t hi = __funnelshift_l(w1, w0, 2 * sh), lo = __funnelshift_l(w2, w1, 2 * sh);
-        const uint64_t fwd = (((uint64_t)hi << 32) | lo) >> (64 - 2 * k);
-        const uint64_t amb48 = ((uint64_t)s_amb[wv][word] << 48) | ((uint64_t)s_amb[wv][word + 1] << 32) |
-                               ((uint64_t)s_amb[wv][word + 2] << 16);
-        const bool ambiguous = ((amb48 << sh) >> (64 - k)) != 0;
+        uint64_t fwd;
+        const bool ambiguous = kmd_window(s_code[wv], s_amb[wv], j, lane, k, fwd);
         const uint64_t w = tile * KMD_TILE + j * 64 + lane;
         bool keep = !ambiguous && w >= a.w_lo && w < a.w_hi;
         const uint64_t rc = ku_revcomp64(fwd, k);
