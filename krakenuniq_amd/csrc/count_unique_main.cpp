@@ -7,41 +7,13 @@
 // outside 4..18 is a usage error (64) where the reference aborts (134) on an uncaught exception; -t is accepted and ignored,
 // also above the processor count, which the reference refuses (64).
 #include <getopt.h>
-#include <sysexits.h>
-#include <unistd.h>
 
 #include <chrono>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/krakenuniq_amd.h"
-#include "ku_seqio.h"
-#include "ku_fasta.h"
+#include "ku_tool.h"
 
-void ku_seqio::fatal(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  fprintf(stderr, "count_unique: ");
-  vfprintf(stderr, fmt, ap);
-  fprintf(stderr, "\n");
-  va_end(ap);
-  exit(code);
-}
-using ku_seqio::fatal;
-
-static int exit_code_of(int st) {
-  switch (st) {
-    case KU_EINVAL: return EX_USAGE;
-    case KU_EDATA: return EX_DATAERR;
-    case KU_ENOINPUT: return EX_NOINPUT;
-    case KU_ENOMEM: return EX_OSERR;
-    default: return EX_SOFTWARE;
-  }
-}
+const char *const ku_tool::name = "count_unique";
+using ku_tool::exit_code_of;
 
 static void usage(int code) {
   fprintf(stderr,
@@ -80,40 +52,21 @@ int main(int argc, char **argv) {
       default: usage(EX_USAGE);
     }
   }
-  std::vector<std::string> inputs;
-  bool from_stdin = optind >= argc;
-  for (int i = optind; i < argc; ++i) {
-    if (strcmp(argv[i], "-") == 0) from_stdin = true;
-    else inputs.push_back(argv[i]);
-  }
-  if (from_stdin && !inputs.empty()) fatal(EX_USAGE, "standard input cannot be combined with files");
-  if (from_stdin) inputs.push_back("/dev/stdin");
-  for (const std::string &path : inputs)
-    if (access(path.c_str(), R_OK) != 0) fatal(EX_NOINPUT, "can't open %s", path.c_str());
+  bool from_stdin = false;
+  const std::vector<std::string> inputs = ku_tool::input_list(argc, argv, optind, from_stdin);
+  ku_tool::require_readable(inputs);
 
   ku_sketch *h = nullptr;
-  const char *dev_env = getenv("KU_DEVICE");
-  int st = ku_sketch_open(dev_env ? atoi(dev_env) : 0, (uint32_t)k, (uint32_t)p, canonical ? KU_SKETCH_CANONICAL : 0u, 0, 1, 0, &h);
+  int st = ku_sketch_open(ku_tool::device(), (uint32_t)k, (uint32_t)p, canonical ? KU_SKETCH_CANONICAL : 0u, 0, 1, 0, &h);
   if (st != KU_OK) fatal(exit_code_of(st), "%s", ku_last_error());
-  auto check = [&](int status) {
-    if (status == KU_OK) return;
-    const std::string msg = ku_last_error();
-    ku_sketch_close(h);
-    fatal(exit_code_of(status), "%s", msg.c_str());
-  };
+  auto check = [&](int status) { ku_tool::check(status, [&] { ku_sketch_close(h); }); };
   const auto t0 = std::chrono::steady_clock::now();
   uint64_t n_records = 0, n_bytes = 0;
-  for (const std::string &path : inputs) {
-    ku_seqio::FastaRecords fa(path);
-    std::string id;
-    const char *seq;
-    size_t len;
-    while (fa.next(id, seq, len)) {
-      check(ku_sketch_add(h, seq, len));
-      ++n_records;
-      n_bytes += len;
-    }
-  }
+  ku_tool::for_each_record(inputs, [&](const std::string &, const char *seq, size_t len) {
+    check(ku_sketch_add(h, seq, len));
+    ++n_records;
+    n_bytes += len;
+  });
   uint64_t estimate = 0, windows = 0;
   check(ku_sketch_estimate(h, &estimate));
   if (verbose) check(ku_sketch_export(h, nullptr, &windows));

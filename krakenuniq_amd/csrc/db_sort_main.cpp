@@ -2,14 +2,10 @@
 // out; the binning, sorting and indexing run on the GPU through ku_db_sort_files (-t and -M are accepted and have
 // nothing left to do).
 #include <getopt.h>
-#include <sysexits.h>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
+#include "ku_tool.h"
 
-#include "../../include/krakenuniq_amd.h"
+const char *const ku_tool::name = "db_sort";
 
 static void usage(int code) {
   fprintf(stderr, "Usage: db_sort [-z] [-M] [-t threads] [-n nt] <-d input db> <-o output db> <-i output idx>\n");
@@ -41,12 +37,10 @@ int main(int argc, char **argv) {
   }
   if (in.empty() || out.empty() || idx.empty()) usage(EX_USAGE);
   fprintf(stderr, "db_sort: Getting database into memory ...");
-  const char *dev_env = getenv("KU_DEVICE");
-  int st = ku_db_sort_files(dev_env ? atoi(dev_env) : 0, in.c_str(), out.c_str(), idx.c_str(), (uint32_t)nt, zero ? 1 : 0);
+  int st = ku_db_sort_files(ku_tool::device(), in.c_str(), out.c_str(), idx.c_str(), (uint32_t)nt, zero ? 1 : 0);
   if (st != KU_OK) {
     fprintf(stderr, "\ndb_sort: %s\n", ku_last_error());
-    return st == KU_EINVAL ? EX_USAGE : st == KU_EDATA ? EX_DATAERR : st == KU_ENOINPUT ? EX_NOINPUT
-           : st == KU_ENOMEM ? EX_OSERR : EX_SOFTWARE;
+    return ku_tool::exit_code_of(st);
   }
   fprintf(stderr, "db_sort: Sorting complete - writing database to disk ...\n");
   return 0;

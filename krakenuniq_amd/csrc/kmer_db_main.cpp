@@ -4,46 +4,21 @@
 // set_lcas's -F file (plain, .gz / BGZF, .bz2); with -P above 1 it is read once per pass.  -P auto reads it once more,
 // beforehand: one HyperLogLog sketch per range of the bin keys (ku_sketch_*) tells the smallest pass count that fits the budget.
 #include <getopt.h>
-#include <sysexits.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/krakenuniq_amd.h"
-#include "ku_seqio.h"
-#include "ku_fasta.h"
+#include "ku_kmerdb_budget.h"
+#include "ku_tool.h"
+
+const char *const ku_tool::name = "kmer_db";
+using ku_tool::exit_code_of;
 
 // the output files once ku_kmerdb_open has created them: a fatal error of the input stage (an unreadable or corrupt library, in
 // whichever pass; possibly on one of the reader's threads) must not leave an unfinished database behind
 static std::string g_unfinished[2];
-
-void ku_seqio::fatal(int code, const char *fmt, ...) {
+static void unlink_unfinished() {
   for (const std::string &path : g_unfinished)
     if (!path.empty()) unlink(path.c_str());
-  va_list ap;
-  va_start(ap, fmt);
-  fprintf(stderr, "kmer_db: ");
-  vfprintf(stderr, fmt, ap);
-  fprintf(stderr, "\n");
-  va_end(ap);
-  exit(code);
-}
-using ku_seqio::fatal;
-
-static int exit_code_of(int st) {
-  switch (st) {
-    case KU_EINVAL: return EX_USAGE;
-    case KU_EDATA: return EX_DATAERR;
-    case KU_ENOINPUT: return EX_NOINPUT;
-    case KU_ENOMEM: return EX_OSERR;
-    default: return EX_SOFTWARE;
-  }
 }
 
 static void usage(int code) {
@@ -90,19 +65,8 @@ static long long plan_passes(int device, uint32_t k, uint32_t nt, const std::vec
   ku_sketch *sk = nullptr;
   int st = ku_sketch_open(device, k, p, KU_SKETCH_CANONICAL, nt, n_groups, 0, &sk);
   if (st != KU_OK) fatal(exit_code_of(st), "%s", ku_last_error());
-  auto check = [&](int status) {
-    if (status == KU_OK) return;
-    const std::string msg = ku_last_error();
-    ku_sketch_close(sk);
-    fatal(exit_code_of(status), "%s", msg.c_str());
-  };
-  for (const std::string &path : inputs) {
-    ku_seqio::FastaRecords fa(path);
-    std::string id;
-    const char *seq;
-    size_t len;
-    while (fa.next(id, seq, len)) check(ku_sketch_add(sk, seq, len));
-  }
+  auto check = [&](int status) { ku_tool::check(status, [&] { ku_sketch_close(sk); }); };
+  ku_tool::for_each_record(inputs, [&](const std::string &, const char *seq, size_t len) { check(ku_sketch_add(sk, seq, len)); });
   std::vector<uint8_t> registers((size_t)n_groups << p);
   check(ku_sketch_export(sk, registers.data(), nullptr));
   ku_sketch_close(sk);
@@ -116,9 +80,7 @@ static long long plan_passes(int device, uint32_t k, uint32_t nt, const std::vec
     if (st != KU_OK) fatal(exit_code_of(st), "%s", msg.c_str());
     device_bytes = got.capacity * 16 + got.segment_bytes;
   }
-  // the budget rule of ku_kmerdb_open; 1/64 of the buffer has to stay free
-  const uint64_t segment = std::min<uint64_t>((uint64_t)64 << 20, device_bytes / 64) & ~(uint64_t)1023;
-  const uint64_t capacity = (device_bytes - segment) / 16, usable = capacity - capacity / 64;
+  const uint64_t usable = ku_kmerdb_budget(device_bytes).usable;
   uint32_t n_passes = 0;
   uint64_t fullest = 0;
   st = ku_sketch_plan_passes(registers.data(), n_groups, p, usable, &n_passes, &fullest);
@@ -160,23 +122,15 @@ int main(int argc, char **argv) {
   if (nt < 1 || nt > 15) fatal(EX_USAGE, "bin key length out of range (-n 1..15)");
   if (k < nt || k > 31) fatal(EX_USAGE, "k-mer length out of range (-k %lld..31)", nt);
   if (passes < 1 || passes > (1ll << (2 * nt))) fatal(EX_USAGE, "-P out of range (1..4^nt)");
-  std::vector<std::string> inputs;
-  bool from_stdin = optind >= argc;
-  for (int i = optind; i < argc; ++i) {
-    if (strcmp(argv[i], "-") == 0) from_stdin = true;
-    else inputs.push_back(argv[i]);
-  }
-  if (from_stdin && !inputs.empty()) fatal(EX_USAGE, "standard input cannot be combined with files");
+  bool from_stdin = false;
+  const std::vector<std::string> inputs = ku_tool::input_list(argc, argv, optind, from_stdin);
   if (from_stdin && auto_passes) fatal(EX_USAGE, "-P auto needs files: the input is read once per pass, standard input can be read only once");
   if (from_stdin && passes > 1) fatal(EX_USAGE, "-P %lld needs files: the input is read once per pass, standard input can be read only once", passes);
-  if (from_stdin) inputs.push_back("/dev/stdin");
 
   // the outputs are created (and whatever was at their paths truncated) when the handle opens: not for an input that is not there
-  for (const std::string &path : inputs)
-    if (access(path.c_str(), R_OK) != 0) fatal(EX_NOINPUT, "can't open %s", path.c_str());
+  ku_tool::require_readable(inputs);
 
-  const char *dev_env = getenv("KU_DEVICE");
-  const int device = dev_env ? atoi(dev_env) : 0;
+  const int device = ku_tool::device();
   if (auto_passes) passes = plan_passes(device, (uint32_t)k, (uint32_t)nt, inputs, kdb_name, idx_name, device_bytes, verbose);
 
   ku_kmerdb *h = nullptr;
@@ -185,25 +139,15 @@ int main(int argc, char **argv) {
   if (st != KU_OK) fatal(exit_code_of(st), "%s", ku_last_error());
   g_unfinished[0] = kdb_name;
   g_unfinished[1] = idx_name;
-  auto check = [&](int status) {
-    if (status == KU_OK) return;
-    const std::string msg = ku_last_error();
-    ku_kmerdb_close(h);  // removes the unfinished files
-    fatal(exit_code_of(status), "%s", msg.c_str());
-  };
+  ku_tool::on_fatal = unlink_unfinished;
+  auto check = [&](int status) { ku_tool::check(status, [&] { ku_kmerdb_close(h); }); };  // (the close removes the unfinished files)
   ku_kmerdb_stats stats{};
   for (long long p = 0; p < passes; ++p) {
     uint64_t n_records = 0;
-    for (const std::string &path : inputs) {
-      ku_seqio::FastaRecords fa(path);
-      std::string id;
-      const char *seq;
-      size_t len;
-      while (fa.next(id, seq, len)) {
-        check(ku_kmerdb_add(h, seq, len));
-        ++n_records;
-      }
-    }
+    ku_tool::for_each_record(inputs, [&](const std::string &, const char *seq, size_t len) {
+      check(ku_kmerdb_add(h, seq, len));
+      ++n_records;
+    });
     check(ku_kmerdb_end_pass(h));
     check(ku_kmerdb_get_stats(h, &stats));
     if (verbose)

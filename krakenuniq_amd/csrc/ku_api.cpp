@@ -3,6 +3,7 @@
 // taxonomy tables and the per-taxon run state.  Compiled with hipcc together with
 // ku_kernels.hip into libkrakenuniq_amd.so.  No CPU classification path exists
 // here: every compute entry point needs a usable gfx950 device.  The C ABI spans six translation units, see ku_ctx.h.
+#include "ku_build.h"
 #include "ku_ctx.h"
 
 // ---------------------------------------------------------------------------- errors
@@ -334,9 +335,7 @@ int ctx_activate(ku_ctx *ctx) {
 extern "C" int ku_ctx_create(int device, ku_ctx **out) {
   if (!out) return fail(KU_EINVAL, "ku_ctx_create: null argument");
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(KU_EHIP, "no HIP device available (this library has no CPU fallback)");
-  if (device < 0 || device >= n) return fail(KU_EINVAL, "device index out of range");
+  KU_TRY(ku_check_device(device));
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
@@ -480,8 +479,7 @@ static void fill_db_dev(DbStore &d, uint64_t n_pairs, uint64_t pair_base, uint32
   d.db.bin_hi = bin_hi;
   d.db.k = k;
   d.db.nt = nt;
-  const uint64_t INDEX2_XOR_MASK = 0xe37e28c4271b5a2dULL;  // krakendb.cpp:45
-  d.db.xor_mask = idx_type == 1 ? 0u : (uint32_t)(INDEX2_XOR_MASK & ((1ull << (2 * nt)) - 1));
+  d.db.xor_mask = idx_type == 1 ? 0u : ku_index2_xor_mask(nt);
 }
 
 // host KrakenDB bins [bin_lo, bin_hi) -> device pairs (12-byte form) + offsets slice

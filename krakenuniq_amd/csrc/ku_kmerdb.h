@@ -1,6 +1,7 @@
-// ku_kmerdb.h -- device code of the k-mer set builder (ku_kmerdb_*, bin/kmer_db; entry points in ku_dbsort.hip): the
-// minimizer bin key shared with db_sort's second half, and the extraction kernel that turns sequence bytes into
-// canonical, unambiguous k-mers (the step the reference leaves to Jellyfish 1, scripts/build_db.sh:140-146).
+// ku_kmerdb.h -- device helpers of the k-mer set builder (ku_kmerdb_*, bin/kmer_db; entry points and the extraction
+// kernel in ku_kmerdb.hip): the minimizer bin key shared with db_sort's second half (ku_dbsort.hip), and the tile decoding
+// that turns sequence bytes into k-mers, shared with the sketch kernel (ku_sketch.hip).  Helpers, constants and argument
+// structs only: a kernel lives in the one .hip file that launches it.
 #pragma once
 #include "ku_device.h"
 
@@ -69,58 +70,3 @@ struct KmdScan {
   unsigned long long *cursor;  // k-mers in the buffer
   uint32_t *err;               // set when a tile would have written past cap (a host-side accounting bug): nothing is written
 };
-
-__global__ __launch_bounds__(64 * KMD_WAVES) void kmerdb_extract_kernel(KmdScan a) {
-  __shared__ uint32_t s_code[KMD_WAVES][KMD_CHUNKS];  // 16 bases per word, the first one in bits 31..30
-  __shared__ uint32_t s_amb[KMD_WAVES][KMD_CHUNKS];   // 16 ambiguity bits per word, the first base in bit 15
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint64_t t0 = a.w_lo / KMD_TILE, t1 = (a.w_hi + KMD_TILE - 1) / KMD_TILE;
-  const uint64_t per_iter = (uint64_t)gridDim.x * KMD_WAVES;
-  const uint64_t n_iter = (t1 - t0 + per_iter - 1) / per_iter;  // the same in every block: the barriers below are uniform
-  const uint32_t k = a.k;
-  for (uint64_t it = 0; it < n_iter; ++it) {
-    const uint64_t tile = t0 + (it * gridDim.x + blockIdx.x) * KMD_WAVES + wv;
-    const bool live = tile < t1;  // wave-uniform
-    if (live) {
-      kmd_pack_tile(a.seq, a.seq_bytes, tile, lane, s_code[wv], s_amb[wv]);
-    }
-    __syncthreads();
-    if (live) {
-      uint64_t canon[KMD_ROUNDS];
-      uint64_t kept[KMD_ROUNDS];  // wave-uniform ballots
-      uint32_t total = 0;
-#pragma unroll
-      for (uint32_t j = 0; j < KMD_ROUNDS; ++j) {
-        uint64_t fwd;
-        const bool ambiguous = kmd_window(s_code[wv], s_amb[wv], j, lane, k, fwd);
-        const uint64_t w = tile * KMD_TILE + j * 64 + lane;
-        bool keep = !ambiguous && w >= a.w_lo && w < a.w_hi;
-        const uint64_t rc = ku_revcomp64(fwd, k);
-        const uint64_t c = fwd < rc ? fwd : rc;
-        if (a.pass_mode && keep) {
-          const uint32_t bin = ku_bin_key(c, k, a.nt, a.xor_mask);
-          keep = bin >= a.bin_lo && bin < a.bin_hi;
-        }
-        canon[j] = c;
-        kept[j] = __ballot(keep);
-        total += (uint32_t)__popcll(kept[j]);
-      }
-      // one reservation per tile; the order inside the buffer is arbitrary, the sort fixes it
-      unsigned long long base = 0;
-      if (lane == 0 && total) base = atomicAdd(a.cursor, (unsigned long long)total);
-      base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
-             (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-      if (base + total > a.cap) {
-        if (lane == 0) atomicOr(a.err, 1u);
-      } else {
-        const uint64_t below = (1ull << lane) - 1;
-#pragma unroll
-        for (uint32_t j = 0; j < KMD_ROUNDS; ++j) {
-          if ((kept[j] >> lane) & 1ull) a.out[base + (uint32_t)__popcll(kept[j] & below)] = canon[j];
-          base += (uint32_t)__popcll(kept[j]);
-        }
-      }
-    }
-    __syncthreads();  // the next tile overwrites the packed words
-  }
-}

@@ -5,15 +5,9 @@
 // Values are kept as taxonomy *nodes* (rank of the taxid in the sorted node universe) while folding; lca() is
 // associative and commutative on the Parent_map forest (default ancestor 1, lca(0, x) = x), so concurrent folds
 // with compare-and-swap give the sequential result.  Offline tool, not on the classify hot path.
-#include <algorithm>
-#include <cstring>
 #include <map>
-#include <string>
-#include <vector>
 
-#include "ku_device.h"
-#include "ku_host.h"
-#include "ku_internal.h"
+#include "ku_build.h"
 
 namespace {
 
@@ -21,10 +15,7 @@ constexpr uint32_t TID_CONTAMINANT1 = 32630;  // 'synthetic construct'   (src/se
 constexpr uint32_t TID_CONTAMINANT2 = 81077;  // 'artificial sequences'
 constexpr uint32_t NO_CONTAM = 0xFFFFFFFFu;
 
-int fail(int code, const std::string &msg) {
-  ku_set_error(msg);
-  return code;
-}
+const KuHipWho SL{"set_lcas: ", "", nullptr};
 
 struct SlDev {
   const uint64_t *kmers;     // key_ct, database order
@@ -153,13 +144,6 @@ struct ku_setlcas {
   std::vector<uint32_t> uid_blocks;                              // {taxid, parent UID} per UID, in creation order: the map file
 };
 
-#define SL_HIP(expr)                                                                                     \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? KU_ENOMEM : KU_EHIP,                   \
-                                      std::string("set_lcas: ") + #expr + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 extern "C" void ku_setlcas_close(ku_setlcas *s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
@@ -174,8 +158,8 @@ extern "C" void ku_setlcas_close(ku_setlcas *s) {
 static int setlcas_open_impl(ku_setlcas *s, const ku_db *db, const ku_tax *tax) {
   ku_db_info info;
   if (ku_db_get_info(db, &info) != KU_OK) return KU_EINVAL;
-  SL_HIP(hipSetDevice(s->device));
-  SL_HIP(hipStreamCreate(&s->stream));
+  KU_HIP(SL, hipSetDevice(s->device));
+  KU_HIP(SL, hipStreamCreate(&s->stream));
   const uint64_t n = info.key_ct, ps = info.key_len + 4, n_bins = info.n_bins;
   s->key_ct = n;
   const uint8_t *pairs = nullptr;
@@ -202,14 +186,14 @@ static int setlcas_open_impl(ku_setlcas *s, const ku_db *db, const ku_tax *tax) 
   s->node_taxid = nodes;
 
   uint8_t *d_raw = nullptr;
-  SL_HIP(hipMalloc((void **)&s->d_kmers, std::max<uint64_t>(n, 1) * 8));
-  SL_HIP(hipMalloc((void **)&s->d_nodes, std::max<uint64_t>(n, 1) * 4));
-  SL_HIP(hipMalloc((void **)&s->d_offsets, (n_bins + 1) * 8));
-  SL_HIP(hipMalloc((void **)&s->d_parent, parent.size() * 4));
-  SL_HIP(hipMalloc((void **)&s->d_node_taxid, nodes.size() * 4));
-  SL_HIP(hipMalloc((void **)&s->d_missing, 8));
-  if (s->flags & KU_SL_FORCE_CONTAMINANT) SL_HIP(hipMalloc((void **)&s->d_contam, std::max<uint64_t>(n, 1) * 4));
-  SL_HIP(hipMalloc((void **)&d_raw, std::max<uint64_t>(n * ps, 1)));
+  KU_HIP(SL, hipMalloc((void **)&s->d_kmers, std::max<uint64_t>(n, 1) * 8));
+  KU_HIP(SL, hipMalloc((void **)&s->d_nodes, std::max<uint64_t>(n, 1) * 4));
+  KU_HIP(SL, hipMalloc((void **)&s->d_offsets, (n_bins + 1) * 8));
+  KU_HIP(SL, hipMalloc((void **)&s->d_parent, parent.size() * 4));
+  KU_HIP(SL, hipMalloc((void **)&s->d_node_taxid, nodes.size() * 4));
+  KU_HIP(SL, hipMalloc((void **)&s->d_missing, 8));
+  if (s->flags & KU_SL_FORCE_CONTAMINANT) KU_HIP(SL, hipMalloc((void **)&s->d_contam, std::max<uint64_t>(n, 1) * 4));
+  KU_HIP(SL, hipMalloc((void **)&d_raw, std::max<uint64_t>(n * ps, 1)));
   hipStream_t st = s->stream;
   hipError_t e = hipSuccess;
   if (n) e = hipMemcpyAsync(d_raw, pairs, n * ps, hipMemcpyHostToDevice, st);
@@ -217,7 +201,7 @@ static int setlcas_open_impl(ku_setlcas *s, const ku_db *db, const ku_tax *tax) 
   if (e == hipSuccess) e = hipMemcpyAsync(s->d_parent, parent.data(), parent.size() * 4, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(s->d_node_taxid, nodes.data(), nodes.size() * 4, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(s->d_missing, 0, 8, st);
-  const unsigned grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 1u << 16);
+  const unsigned grid = ku_grid_256(n);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(setlcas_unpack_kernel, dim3(grid), dim3(256), 0, st, d_raw, n, info.key_len, s->d_kmers, s->d_nodes);
     hipLaunchKernelGGL(setlcas_to_nodes_kernel, dim3(grid), dim3(256), 0, st, s->d_nodes, n, s->d_node_taxid,
@@ -226,10 +210,9 @@ static int setlcas_open_impl(ku_setlcas *s, const ku_db *db, const ku_tax *tax) 
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   (void)hipFree(d_raw);
-  SL_HIP(e);
-  const uint64_t INDEX2_XOR_MASK = 0xe37e28c4271b5a2dULL;  // krakendb.cpp:45
+  KU_HIP(SL, e);
   s->dev = SlDev{s->d_kmers, s->d_nodes, s->d_contam, s->d_offsets, s->d_parent, info.k, info.nt,
-                 info.idx_type == 1 ? 0u : (uint32_t)(INDEX2_XOR_MASK & (n_bins - 1))};
+                 info.idx_type == 1 ? 0u : ku_index2_xor_mask(info.nt)};
   if (s->flags & KU_SL_UIDS) {  // the values as they are in the file (UIDs of an earlier run would need that run's map: uid_mapping exits on them)
     s->h_uids.resize(n);
     for (uint64_t i = 0; i < n; ++i) memcpy(&s->h_uids[i], pairs + i * ps + info.key_len, 4);
@@ -240,9 +223,7 @@ static int setlcas_open_impl(ku_setlcas *s, const ku_db *db, const ku_tax *tax) 
 extern "C" int ku_setlcas_open(int device, const ku_db *db, const ku_tax *tax, uint32_t flags, ku_setlcas **out) {
   if (!db || !tax || !out) return fail(KU_EINVAL, "ku_setlcas_open: null argument");
   *out = nullptr;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(KU_EHIP, "no HIP device available (this library has no CPU fallback)");
-  if (device < 0 || device >= n_dev) return fail(KU_EINVAL, "device index out of range");
+  KU_TRY(ku_check_device(device));
   ku_setlcas *s = new ku_setlcas();
   s->device = device;
   s->flags = flags;
@@ -254,7 +235,7 @@ extern "C" int ku_setlcas_open(int device, const ku_db *db, const ku_tax *tax, u
 
 extern "C" int ku_setlcas_add(ku_setlcas *s, const char *seq, uint64_t len, uint32_t taxid) {
   if (!s || (len && !seq)) return fail(KU_EINVAL, "ku_setlcas_add: null argument");
-  SL_HIP(hipSetDevice(s->device));
+  KU_HIP(SL, hipSetDevice(s->device));
   s->order++;
   if (len < s->dev.k) return KU_OK;
   const auto it = std::lower_bound(s->node_taxid.begin(), s->node_taxid.end(), taxid);
@@ -262,16 +243,16 @@ extern "C" int ku_setlcas_add(ku_setlcas *s, const char *seq, uint64_t len, uint
     return fail(KU_EINVAL, "ku_setlcas_add: taxid " + std::to_string(taxid) + " is neither in the taxonomy nor a database value");
   const uint32_t node = (uint32_t)(it - s->node_taxid.begin());
   if (len > s->seq_cap) {
-    SL_HIP(hipStreamSynchronize(s->stream));
+    KU_HIP(SL, hipStreamSynchronize(s->stream));
     if (s->d_seq) (void)hipFree(s->d_seq);
     s->d_seq = nullptr;
     s->seq_cap = 0;
     const uint64_t want = len + len / 4 + 4096;
-    SL_HIP(hipMalloc((void **)&s->d_seq, want));
+    KU_HIP(SL, hipMalloc((void **)&s->d_seq, want));
     s->seq_cap = want;
   }
   // the previous sequence's kernel reads d_seq: the copy is ordered behind it on the same stream
-  SL_HIP(hipMemcpyAsync(s->d_seq, seq, len, hipMemcpyHostToDevice, s->stream));
+  KU_HIP(SL, hipMemcpyAsync(s->d_seq, seq, len, hipMemcpyHostToDevice, s->stream));
   uint32_t mode = 0, code = 0;
   if (s->flags & KU_SL_UIDS) {
     // -I (src/set_lcas.cpp:451-455): value = uid_mapping(value, taxid) for every k-mer of the sequence IN ORDER -- a new set
@@ -282,15 +263,15 @@ extern "C" int ku_setlcas_add(ku_setlcas *s, const char *seq, uint64_t len, uint
       if (s->d_where) (void)hipFree(s->d_where);
       s->d_where = nullptr;
       s->where_cap = 0;
-      SL_HIP(hipMalloc((void **)&s->d_where, (n + n / 4 + 1024) * 8));
+      KU_HIP(SL, hipMalloc((void **)&s->d_where, (n + n / 4 + 1024) * 8));
       s->where_cap = n + n / 4 + 1024;
     }
-    const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16);
+    const unsigned grid = ku_grid_256(n);  // n >= 1
     hipLaunchKernelGGL(setlcas_kernel, dim3(grid), dim3(256), 0, s->stream, s->dev, s->d_seq, len, node, 3u, 0u, s->d_missing, s->d_where);
-    SL_HIP(hipGetLastError());
+    KU_HIP(SL, hipGetLastError());
     s->h_where.resize(n);
-    SL_HIP(hipMemcpyAsync(s->h_where.data(), s->d_where, n * 8, hipMemcpyDeviceToHost, s->stream));
-    SL_HIP(hipStreamSynchronize(s->stream));
+    KU_HIP(SL, hipMemcpyAsync(s->h_where.data(), s->d_where, n * 8, hipMemcpyDeviceToHost, s->stream));
+    KU_HIP(SL, hipStreamSynchronize(s->stream));
     // within a sequence the taxid is fixed: uid_mapping(old, taxid) is a function of the old UID alone
     std::map<uint32_t, uint32_t> memo;
     for (uint64_t p = 0; p < n; ++p) {
@@ -336,11 +317,11 @@ extern "C" int ku_setlcas_add(ku_setlcas *s, const char *seq, uint64_t len, uint
     code = s->order * 2u + (taxid == TID_CONTAMINANT2 ? 1u : 0u);
   }
   const uint64_t n = len - s->dev.k + 1;
-  const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16);
+  const unsigned grid = ku_grid_256(n);  // n >= 1
   hipLaunchKernelGGL(setlcas_kernel, dim3(grid), dim3(256), 0, s->stream, s->dev, s->d_seq, len, node, mode, code,
                      s->d_missing, (unsigned long long *)nullptr);
-  SL_HIP(hipGetLastError());
-  SL_HIP(hipStreamSynchronize(s->stream));  // `seq` may be reused by the caller; offline tool, no pipelining needed
+  KU_HIP(SL, hipGetLastError());
+  KU_HIP(SL, hipStreamSynchronize(s->stream));  // `seq` may be reused by the caller; offline tool, no pipelining needed
   return KU_OK;
 }
 
@@ -354,29 +335,29 @@ extern "C" int ku_setlcas_uid_map(const ku_setlcas *s, const uint32_t **blocks, 
 
 extern "C" int ku_setlcas_finish(ku_setlcas *s, uint32_t *values_out, uint64_t *n_missing) {
   if (!s || (s->key_ct && !values_out)) return fail(KU_EINVAL, "ku_setlcas_finish: null argument");
-  SL_HIP(hipSetDevice(s->device));
+  KU_HIP(SL, hipSetDevice(s->device));
   const uint64_t n = s->key_ct;
   if (s->flags & KU_SL_UIDS) {
     unsigned long long miss = 0;
-    SL_HIP(hipMemcpyAsync(&miss, s->d_missing, 8, hipMemcpyDeviceToHost, s->stream));
-    SL_HIP(hipStreamSynchronize(s->stream));
+    KU_HIP(SL, hipMemcpyAsync(&miss, s->d_missing, 8, hipMemcpyDeviceToHost, s->stream));
+    KU_HIP(SL, hipStreamSynchronize(s->stream));
     if (n) memcpy(values_out, s->h_uids.data(), n * 4);
     if (n_missing) *n_missing = miss;
     return KU_OK;
   }
-  const unsigned grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 1u << 16);
+  const unsigned grid = ku_grid_256(n);
   hipLaunchKernelGGL(setlcas_to_taxids_kernel, dim3(grid), dim3(256), 0, s->stream, s->d_nodes, n, s->d_node_taxid,
                      s->d_contam);
-  SL_HIP(hipGetLastError());
+  KU_HIP(SL, hipGetLastError());
   unsigned long long miss = 0;
-  SL_HIP(hipMemcpyAsync(&miss, s->d_missing, 8, hipMemcpyDeviceToHost, s->stream));
-  if (n) SL_HIP(hipMemcpyAsync(values_out, s->d_nodes, n * 4, hipMemcpyDeviceToHost, s->stream));
-  SL_HIP(hipStreamSynchronize(s->stream));
+  KU_HIP(SL, hipMemcpyAsync(&miss, s->d_missing, 8, hipMemcpyDeviceToHost, s->stream));
+  if (n) KU_HIP(SL, hipMemcpyAsync(values_out, s->d_nodes, n * 4, hipMemcpyDeviceToHost, s->stream));
+  KU_HIP(SL, hipStreamSynchronize(s->stream));
   if (n_missing) *n_missing = miss;
   // back to nodes, so that further sequences can be added after a snapshot
   hipLaunchKernelGGL(setlcas_to_nodes_kernel, dim3(grid), dim3(256), 0, s->stream, s->d_nodes, n, s->d_node_taxid,
                      (uint32_t)s->node_taxid.size(), (uint32_t *)nullptr);
-  SL_HIP(hipGetLastError());
-  SL_HIP(hipStreamSynchronize(s->stream));
+  KU_HIP(SL, hipGetLastError());
+  KU_HIP(SL, hipStreamSynchronize(s->stream));
   return KU_OK;
 }

@@ -3,50 +3,17 @@
 // and have nothing left to do; -I: UID databases, the set numbering of the reference on one thread).  Unlike the reference without -M, the
 // input database file is never modified when -o names another file.
 #include <getopt.h>
-#include <sysexits.h>
-#include <unistd.h>
 
 #include <cctype>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <fstream>
 #include <map>
 #include <sstream>
-#include <string>
 #include <unordered_map>
-#include <vector>
 
-#include "../../include/krakenuniq_amd.h"
-#include "ku_seqio.h"
-#include "ku_fasta.h"
+#include "ku_tool.h"
 
-void ku_seqio::fatal(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  fprintf(stderr, "set_lcas: ");
-  vfprintf(stderr, fmt, ap);
-  fprintf(stderr, "\n");
-  va_end(ap);
-  exit(code);
-}
-using ku_seqio::fatal;
-
-static int exit_code_of(int st) {
-  switch (st) {
-    case KU_EINVAL: return EX_USAGE;
-    case KU_EDATA: return EX_DATAERR;
-    case KU_ENOINPUT: return EX_NOINPUT;
-    case KU_ENOMEM: return EX_OSERR;
-    default: return EX_SOFTWARE;
-  }
-}
-#define CHECK(expr)                                                  \
-  do {                                                               \
-    int st_ = (expr);                                                \
-    if (st_ != KU_OK) fatal(exit_code_of(st_), "%s", ku_last_error()); \
-  } while (0)
+const char *const ku_tool::name = "set_lcas";
+#define CHECK(expr) ku_tool::check((expr), [] {})
 
 static void usage(int code) {
   fprintf(stderr,
@@ -225,8 +192,7 @@ int main(int argc, char **argv) {
     std::vector<uint32_t> ids, parents;  // the (extended) taxonomy as the library takes it
     for (const auto &kv : tt.entries) { ids.push_back(kv.first); parents.push_back(kv.second.file_parent); }
     CHECK(ku_tax_from_arrays(ids.data(), parents.data(), ids.size(), &tax));
-    const char *dev_env = getenv("KU_DEVICE");
-    CHECK(ku_setlcas_open(dev_env ? atoi(dev_env) : 0, db, tax, (reset ? KU_SL_RESET : 0u) | (force_contaminant ? KU_SL_FORCE_CONTAMINANT : 0u) | (uid_map_name.empty() ? 0u : KU_SL_UIDS), &sl));
+    CHECK(ku_setlcas_open(ku_tool::device(), db, tax, (reset ? KU_SL_RESET : 0u) | (force_contaminant ? KU_SL_FORCE_CONTAMINANT : 0u) | (uid_map_name.empty() ? 0u : KU_SL_UIDS), &sl));
   }
   // Parent_map membership (src/set_lcas.cpp:313-318,338): taxids with an entry in taxDB
   auto in_taxonomy = [&](uint32_t taxid) { return taxid != 0 && tt.has(taxid); };

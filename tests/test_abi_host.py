@@ -78,6 +78,31 @@ def test_no_cpu_fallback_without_gpu():
     assert e.value.status == -5
 
 
+@pytest.mark.gpu
+def test_build_entry_points_refuse_a_device_that_is_not_there(f1, tmp_path):
+    """the device check the four build-side entry points share: an index below 0 or past the last device is KU_EINVAL with
+    "device index out of range", before any output file is created and without a handle left behind"""
+    import ctypes as C
+
+    L = capi.lib()
+    jdb, kdb, idx = (os.fsencode(str(tmp_path / n)) for n in ("in.jdb", "out.kdb", "out.idx"))
+    synth.write_jdb(jdb.decode(), np.arange(1, 6, dtype=np.uint64), np.zeros(5, dtype=np.uint32), 31)
+    for device in (-1, L.ku_device_count()):
+        h = C.c_void_p(0xDEAD)  # every open resets its out-parameter before it looks at the device
+        calls = {
+            "ku_db_sort_files": lambda: L.ku_db_sort_files(device, jdb, kdb, idx, 7, 0),
+            "ku_kmerdb_open": lambda: L.ku_kmerdb_open(device, 31, 7, 1, 1 << 20, kdb, idx, C.byref(h)),
+            "ku_sketch_open": lambda: L.ku_sketch_open(device, 31, 12, 0, 0, 1, 0, C.byref(h)),
+            "ku_setlcas_open": lambda: L.ku_setlcas_open(device, f1["db"].h, f1["tax"].h, 0, C.byref(h)),
+        }
+        for name, call in calls.items():
+            h.value = 0xDEAD
+            assert call() == -1, (name, device)  # KU_EINVAL
+            assert L.ku_last_error().decode() == "device index out of range", (name, device)
+            assert name == "ku_db_sort_files" or h.value is None, (name, device)
+            assert sorted(os.listdir(tmp_path)) == ["in.jdb"], (name, device)
+
+
 def test_db_open_and_errors(f1, tmp_path):
     i = f1["db"].info
     assert (i.k, i.nt, i.idx_type, i.key_len, i.n_bins) == (31, 7, 2, 8, 4 ** 7)

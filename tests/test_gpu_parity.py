@@ -156,6 +156,7 @@ def test_sharded_lookup_merges_to_unsharded(f1, n_shards):
         ctx, _, _ = make_ctx(cdb=f1["cdb"], ctax=f1["ctax"], shard=(int(bounds[s]), int(bounds[s + 1])),
                              all_values=all_values)
         t_taxa = torch.zeros(len(buf), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()  # torch fills on its stream; the library works on the context's own, which does not wait for it
         ctx.lookup_device(t_seq.data_ptr(), len(buf), t_taxa.data_ptr(), flags=capi.KU_F_KEEP_SLOTS)
         ctx.synchronize()
         u = t_taxa.view(torch.int32).cpu().numpy().view(np.uint32)
@@ -164,6 +165,7 @@ def test_sharded_lookup_merges_to_unsharded(f1, n_shards):
     # exactly one shard may be non-zero per k-mer -> max == the owner's value; resolve on shard 0's context
     t_m = torch.from_numpy(merged.view(np.int32)).to(dev)
     t_calls = torch.zeros(len(lens), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()  # as above: the fill must have landed before the context's stream writes the calls
     ctxs[0].resolve_device(t_seq.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), len(lens), t_calls.data_ptr(),
                            t_m.data_ptr(), max_read_len=int(lens.max()))
     ctxs[0].synchronize()
