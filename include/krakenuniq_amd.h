@@ -138,6 +138,49 @@ int ku_kmerdb_finish(ku_kmerdb *h, uint64_t *key_ct);
 int ku_kmerdb_get_stats(const ku_kmerdb *h, ku_kmerdb_stats *out);
 void ku_kmerdb_close(ku_kmerdb *h);
 
+/* The union of 2..8 sorted databases as one sorted database: what adding a library to a database needs, without building
+ * the database again.  The inputs are database.kdb / database.idx pairs that share k, key_len, nt and the index type; each is
+ * in (minimizer bin key, k-mer) order (src/db_sort.cpp:34-128), which the output keeps, so the union is a merge by rank on the
+ * device, bin by bin, and no bin key is computed.  A k-mer that several inputs hold is written once.  Its value: with a
+ * taxonomy, lca(Parent_map, vA, vB) (krakenutil.cpp:90-118) over the node universe taxDB ids U {0, 1} U every input value --
+ * the fold of set_lcas (src/set_lcas.cpp:429-476), which is associative and commutative with lca(0, x) = x, so
+ *   kmer_db(A U B)                    == db_merge(kmer_db(A), kmer_db(B))
+ *   set_lcas(kmer_db(A U B), A U B)   == db_merge with taxDB (set_lcas(kmer_db(A), A), set_lcas(kmer_db(B), B))
+ *                                     == set_lcas over B alone of db_merge(set_lcas(kmer_db(A), A), kmer_db(B))
+ * byte for byte.  Without a taxonomy (tax = NULL) equal values stay, a 0 yields to the other value, and two different non-zero
+ * values are KU_EDATA ("values differ for a k-mer present in both inputs; a taxonomy is needed to fold them").  More than two
+ * inputs are folded left to right.  The database header is input 0's with the key count replaced; the index is written as
+ * ku_db_sort_files writes it, with the inputs' index type.
+ *
+ * The run is cut into chunks, contiguous ranges of bins: from its first bin a chunk takes the longest range whose records, all
+ * inputs counted together, number at most `capacity` and whose bins number at most `max_bins`, where
+ *   max_bins = device_bytes / 8 / 24 - 1,   capacity = (device_bytes - device_bytes / 8) / 56
+ * (per bin 3 offset slices of 8 bytes; per record 12 bytes each in the buffers of the left side, of the input being merged and
+ * of the result, 8 of rank, 8 of scanned duplicate count, 1 of flag, 3 spare).  device_bytes = 0: half of the HBM that is free;
+ * below KU_DBMERGE_MIN_BYTES: KU_EINVAL.  A single bin with more records than `capacity` is KU_ENOMEM (ku_last_error names -s).
+ * Every budget gives the same files.
+ *
+ * Checked before any device is touched and before any output is created: null arguments, n_inputs outside 2..8, the budget
+ * (KU_EINVAL); inputs that cannot be read (KU_ENOINPUT / KU_EDATA as ku_db_open reports them); inputs that disagree in k,
+ * key_len, nt or idx_type (KU_EINVAL; the message names both files and db_sort -n, which re-indexes a database); an output
+ * path that names the same file as an input (device and inode compared; KU_EINVAL).  Then the device: KU_EHIP without one,
+ * KU_EINVAL "device index out of range".  A call that fails after it created the outputs removes them.  UID databases
+ * (set_lcas -I) cannot be merged this way: their values are set numbers, not taxa.  stats may be null. */
+#define KU_DBMERGE_MIN_BYTES 65536
+struct ku_tax; /* the taxonomy object, ku_tax below */
+typedef struct ku_db_merge_stats {
+  uint64_t key_ct;        /* records written */
+  uint64_t duplicates;    /* input records that met an equal k-mer (sum over the fold steps) */
+  uint64_t folded;        /* duplicates whose two values differed and were both non-zero */
+  uint64_t chunks;        /* bin ranges the run was cut into */
+  uint64_t capacity;      /* records per chunk under the budget */
+  double upload_s, merge_s, write_s; /* host clock around the (synchronous) stages: host to device; kernels and scan; device
+                                      * to host and file output */
+} ku_db_merge_stats;
+int ku_db_merge_files(int device, const char *const *kdb_paths, const char *const *idx_paths, uint32_t n_inputs,
+                      const struct ku_tax *tax /* or NULL */, uint64_t device_bytes, const char *out_kdb_path,
+                      const char *out_idx_path, ku_db_merge_stats *stats /* or NULL */);
+
 /* HyperLogLog sketches of a library's k-mers on the device: the reference's count_unique (src/count_unique.cpp, called by
  * scripts/build_db.sh:127 to size the Jellyfish hash), and the per-range estimates from which kmer_db -P auto plans its passes.
  *

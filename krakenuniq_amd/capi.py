@@ -93,6 +93,8 @@ SIGNATURES = {
     "ku_setlcas_uid_map": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint64)]),
     "ku_setlcas_close": (None, [C.c_void_p]),
     "ku_db_sort_files": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int]),
+    "ku_db_merge_files": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_uint32, C.c_void_p, C.c_uint64,
+                                    C.c_char_p, C.c_char_p, C.c_void_p]),
     "ku_kmerdb_open": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "ku_kmerdb_add": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64]),
     "ku_kmerdb_end_pass": (C.c_int, [C.c_void_p]),
@@ -935,6 +937,35 @@ def kmer_db_files(fasta_seqs, out_kdb, out_idx, k, nt, passes=1, device_bytes=0,
                 b.add(s)
             per_pass.append(b.end_pass())
         return b.finish(), per_pass
+
+
+class DbMergeStats(C.Structure):  # ku_db_merge_stats
+    _fields_ = [(n, C.c_uint64) for n in ("key_ct", "duplicates", "folded", "chunks", "capacity")] + \
+               [(n, C.c_double) for n in ("upload_s", "merge_s", "write_s")]
+
+
+KU_DBMERGE_MIN_BYTES = 65536
+
+
+def db_merge_capacity(device_bytes):
+    """the budget rule of ku_db_merge_files: (records of all inputs together that a chunk may hold, bins it may span).  One
+    eighth of the budget is the bins' (3 offset slices of 8 bytes, each with a closing entry), the rest the records' at 56
+    bytes each"""
+    bin_bytes = device_bytes // 8
+    return (device_bytes - bin_bytes) // 56, bin_bytes // 24 - 1
+
+
+def db_merge_files(kdb_paths, idx_paths, out_kdb, out_idx, tax=None, device_bytes=0, device=0):
+    """the union of 2..8 sorted databases (ku_db_merge_files); tax: a Tax to fold the values of shared k-mers with lca(), or
+    None (such values then have to be equal, or all but one of them 0).  Returns the DbMergeStats"""
+    assert len(kdb_paths) == len(idx_paths)
+    n = len(kdb_paths)
+    kdbs = (C.c_char_p * max(n, 1))(*[os.fsencode(p) for p in kdb_paths])
+    idxs = (C.c_char_p * max(n, 1))(*[os.fsencode(p) for p in idx_paths])
+    st = DbMergeStats()
+    _chk(lib().ku_db_merge_files(device, kdbs, idxs, n, tax.h if tax is not None else None, device_bytes, os.fsencode(out_kdb),
+                                 os.fsencode(out_idx), C.byref(st)), "ku_db_merge_files")
+    return st
 
 
 KU_SKETCH_CANONICAL = 1

@@ -40,19 +40,6 @@ static void usage(int code) {
   exit(code);
 }
 
-static bool parse_bytes(const char *txt, uint64_t &out) {
-  char *end = nullptr;
-  const unsigned long long v = strtoull(txt, &end, 10);
-  if (end == txt || *txt == '-') return false;
-  uint64_t mul = 1;
-  if (*end == 'K' || *end == 'k') mul = 1ull << 10, ++end;
-  else if (*end == 'M' || *end == 'm') mul = 1ull << 20, ++end;
-  else if (*end == 'G' || *end == 'g') mul = 1ull << 30, ++end;
-  if (*end) return false;
-  out = v * mul;
-  return true;
-}
-
 // -P auto: one sketch of the canonical k-mers per range of the bin keys (min(1024, 4^nt) ranges, p = 12), taken in a pass of its
 // own and closed before the builder measures the free memory; then the smallest power-of-two pass count whose fullest pass
 // fits the collection buffer of the budget with a tenth to spare (ku_sketch_plan_passes).  Without -s the budget is half of
@@ -110,7 +97,7 @@ int main(int argc, char **argv) {
         passes = auto_passes ? 1 : atoll(optarg);
         break;
       case 's':
-        if (!parse_bytes(optarg, device_bytes) || device_bytes == 0) fatal(EX_USAGE, "-s takes a positive size, such as 512M or 8G");
+        if (!ku_tool::parse_bytes(optarg, device_bytes) || device_bytes == 0) fatal(EX_USAGE, "-s takes a positive size, such as 512M or 8G");
         break;
       case 't': if (atoll(optarg) <= 0) fatal(EX_USAGE, "can't use nonpositive thread count"); break;
       case 'v': verbose = true; break;

@@ -1,4 +1,4 @@
-// ku_build.h -- host plumbing shared by the database build tools' translation units (ku_dbsort.hip, ku_kmerdb.hip,
+// ku_build.h -- host plumbing shared by the database build tools' translation units (ku_dbsort.hip, ku_kmerdb.hip, ku_dbmerge.hip,
 // ku_sketch.hip, ku_setlcas.hip): the device check, the KRAKIX2 scramble mask, the HIP check, launch geometry, rocPRIM's
 // two-call protocol, and what the builder borrows from db_sort.  `fail` and KU_TRY are those of ku_ctx.h.  Not part of the
 // public ABI.

@@ -1,6 +1,6 @@
-// ku_tool.h -- what the database build programs share (db_sort, set_lcas, kmer_db, count_unique): the fatal exit of the
-// program and of its input stage, the exit code of a library status, the device to use, the list of input files, and the
-// loop over their FASTA records.  Plain C++ over the C ABI, no HIP.
+// ku_tool.h -- what the database build programs share (db_sort, set_lcas, kmer_db, count_unique, db_merge): the fatal exit of the
+// program and of its input stage, the exit code of a library status, the device to use, the size that -s takes, the list of input
+// files, and the loop over their FASTA records.  Plain C++ over the C ABI, no HIP.
 #pragma once
 #include <sysexits.h>
 #include <unistd.h>
@@ -34,6 +34,20 @@ inline int exit_code_of(int st) {
 inline int device() {  // KU_DEVICE selects the GPU
   const char *dev_env = getenv("KU_DEVICE");
   return dev_env ? atoi(dev_env) : 0;
+}
+
+// a byte count with an optional K / M / G suffix (powers of 1024), as -s takes it
+inline bool parse_bytes(const char *txt, uint64_t &out) {
+  char *end = nullptr;
+  const unsigned long long v = strtoull(txt, &end, 10);
+  if (end == txt || *txt == '-') return false;
+  uint64_t mul = 1;
+  if (*end == 'K' || *end == 'k') mul = 1ull << 10, ++end;
+  else if (*end == 'M' || *end == 'm') mul = 1ull << 20, ++end;
+  else if (*end == 'G' || *end == 'g') mul = 1ull << 30, ++end;
+  if (*end) return false;
+  out = v * mul;
+  return true;
 }
 
 }  // namespace ku_tool
