@@ -32,7 +32,6 @@ const KuHipWho DM{"db_merge: ", " -- db_merge: use a smaller budget (-s)", nullp
 
 constexpr uint32_t MG_ERR_VALUES = 1u;  // two different non-zero values of one k-mer, and no taxonomy to fold them
 constexpr uint32_t MG_ERR_INDEX = 2u;   // offsets that do not ascend or leave the slice
-constexpr size_t MG_IO_CHUNK = (size_t)64 << 20;
 
 // one side of a fold step: n records of the chunk in their on-disk form, and the offsets of the chunk's bins (nb + 1
 // entries; off[b] - base = index of the first record of bin b within `raw`)
@@ -48,42 +47,6 @@ struct MgFold {
   const uint32_t *node_taxid;  // sorted node universe
   uint32_t n_nodes;
 };
-
-struct __attribute__((packed, aligned(4))) MgKey8 { uint32_t lo, hi; };
-struct __attribute__((packed, aligned(4))) MgRec12 { uint32_t lo, hi, val; };
-
-__device__ __forceinline__ uint64_t mg_key(const uint8_t *__restrict__ raw, uint64_t i, uint32_t key_len) {
-  if (key_len == 8) {
-    const MgKey8 r = *reinterpret_cast<const MgKey8 *>(raw + i * 12);
-    return (uint64_t)r.hi << 32 | r.lo;
-  }
-  const uint8_t *p = raw + i * (key_len + 4);
-  uint64_t key = 0;
-  for (uint32_t b = 0; b < key_len; ++b) key |= (uint64_t)p[b] << (8 * b);
-  return key;
-}
-__device__ __forceinline__ void mg_load(const uint8_t *__restrict__ raw, uint64_t i, uint32_t key_len, uint64_t &key, uint32_t &val) {
-  if (key_len == 8) {
-    const MgRec12 r = *reinterpret_cast<const MgRec12 *>(raw + i * 12);
-    key = (uint64_t)r.hi << 32 | r.lo;
-    val = r.val;
-    return;
-  }
-  const uint8_t *p = raw + i * (key_len + 4);
-  key = 0;
-  val = 0;
-  for (uint32_t b = 0; b < key_len; ++b) key |= (uint64_t)p[b] << (8 * b);
-  for (uint32_t b = 0; b < 4; ++b) val |= (uint32_t)p[key_len + b] << (8 * b);
-}
-__device__ __forceinline__ void mg_store(uint8_t *raw, uint64_t i, uint32_t key_len, uint64_t key, uint32_t val) {
-  if (key_len == 8) {
-    *reinterpret_cast<MgRec12 *>(raw + i * 12) = MgRec12{(uint32_t)key, (uint32_t)(key >> 32), val};
-    return;
-  }
-  uint8_t *p = raw + i * (key_len + 4);
-  for (uint32_t b = 0; b < key_len; ++b) p[b] = (uint8_t)(key >> (8 * b));
-  for (uint32_t b = 0; b < 4; ++b) p[key_len + b] = (uint8_t)(val >> (8 * b));
-}
 
 // the bin of record j (j < s.n, nb >= 1): the b with off[b] <= base + j < off[b + 1]
 __device__ __forceinline__ uint64_t mg_bin_of(const MgSide &s, uint64_t nb, uint64_t j) {
@@ -107,17 +70,14 @@ __device__ __forceinline__ uint64_t mg_lower_bound(const uint8_t *__restrict__ r
                                                    uint32_t key_len) {
   while (lo < hi) {
     const uint64_t mid = (lo + hi) >> 1;
-    if (mg_key(raw, mid, key_len) < key) lo = mid + 1; else hi = mid;
+    if (ku_rec_key(raw, mid, key_len) < key) lo = mid + 1; else hi = mid;
   }
   return lo;
 }
+// (the node universe holds every value of every input: the clamp is never taken)
 __device__ __forceinline__ uint32_t mg_node_of(const MgFold &f, uint32_t taxid) {
-  uint32_t lo = 0, hi = f.n_nodes;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (f.node_taxid[mid] < taxid) lo = mid + 1; else hi = mid;
-  }
-  return lo < f.n_nodes ? lo : 0;  // (the node universe holds every value of every input)
+  const uint32_t node = ku_node_of(f.node_taxid, f.n_nodes, taxid);
+  return node < f.n_nodes ? node : 0;
 }
 
 // step 1: B's records ranked in A
@@ -129,10 +89,10 @@ __global__ void dbmerge_rank_b_kernel(MgSide A, MgSide B, uint64_t nb, uint32_t 
     const uint64_t b = mg_bin_of(B, nb, j);
     uint64_t lo, hi;
     mg_slice(A, b, lo, hi, err);
-    const uint64_t key = mg_key(B.raw, j, key_len);
+    const uint64_t key = ku_rec_key(B.raw, j, key_len);
     const uint64_t at = mg_lower_bound(A.raw, lo, hi, key, key_len);
     rank[j] = at;
-    dup[j] = at < hi && mg_key(A.raw, at, key_len) == key;
+    dup[j] = at < hi && ku_rec_key(A.raw, at, key_len) == key;
   }
 }
 
@@ -143,9 +103,9 @@ __global__ void dbmerge_scatter_b_kernel(MgSide B, uint32_t key_len, const uint6
     if (dup[j]) continue;
     uint64_t key;
     uint32_t val;
-    mg_load(B.raw, j, key_len, key, val);
+    ku_rec_load(B.raw, j, key_len, key, val);
     const uint64_t at = rank[j] + j - dups_before[j];
-    if (at < out_cap) mg_store(out, at, key_len, key, val);
+    if (at < out_cap) ku_rec_store(out, at, key_len, key, val);
   }
 }
 
@@ -158,12 +118,12 @@ __global__ void dbmerge_scatter_a_kernel(MgSide A, MgSide B, uint64_t nb, uint32
     mg_slice(B, b, lo, hi, err);
     uint64_t key;
     uint32_t val;
-    mg_load(A.raw, i, key_len, key, val);
+    ku_rec_load(A.raw, i, key_len, key, val);
     const uint64_t at = mg_lower_bound(B.raw, lo, hi, key, key_len);
     if (at < hi) {
       uint64_t key_b;
       uint32_t val_b;
-      mg_load(B.raw, at, key_len, key_b, val_b);
+      ku_rec_load(B.raw, at, key_len, key_b, val_b);
       if (key_b == key && val_b != val) {
         if (val == 0 || val_b == 0) val |= val_b;  // lca(0, x) = x
         else {
@@ -174,7 +134,7 @@ __global__ void dbmerge_scatter_a_kernel(MgSide A, MgSide B, uint64_t nb, uint32
       }
     }
     const uint64_t to = i + at - dups_before[at];
-    if (to < out_cap) mg_store(out, to, key_len, key, val);
+    if (to < out_cap) ku_rec_store(out, to, key_len, key, val);
   }
 }
 
@@ -191,12 +151,6 @@ struct MgWiden {
   __device__ uint64_t operator()(uint8_t x) const { return x; }
 };
 
-double mg_now() {
-  struct timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 // the inputs of a run, closed on every exit path
 struct MgInputs {
   std::vector<ku_db *> dbs;
@@ -205,40 +159,7 @@ struct MgInputs {
   }
 };
 
-// the outputs of a run: removed unless the run completed
-struct MgOutputs {
-  std::string kdb_path, idx_path;
-  int kdb_fd = -1, idx_fd = -1;
-  // the end of a complete run: true when both files closed without an error (they stay); false leaves them to the destructor
-  bool close_both() {
-    const bool bad_kdb = ::close(kdb_fd) != 0, bad_idx = ::close(idx_fd) != 0;
-    kdb_fd = idx_fd = -1;
-    if (bad_kdb || bad_idx) {
-      ::unlink(kdb_path.c_str());
-      ::unlink(idx_path.c_str());
-      return false;
-    }
-    return true;
-  }
-  ~MgOutputs() {
-    if (kdb_fd >= 0) { ::close(kdb_fd); ::unlink(kdb_path.c_str()); }
-    if (idx_fd >= 0) { ::close(idx_fd); ::unlink(idx_path.c_str()); }
-  }
-};
-
 bool mg_same_file(const struct stat &a, const struct stat &b) { return a.st_dev == b.st_dev && a.st_ino == b.st_ino; }
-
-// device -> file in pieces
-int mg_write_from_device(int fd, const std::string &path, const void *d_src, uint64_t bytes, std::vector<uint8_t> &h_buf) {
-  for (uint64_t at = 0; at < bytes;) {
-    const size_t part = (size_t)std::min<uint64_t>(MG_IO_CHUNK, bytes - at);
-    if (h_buf.size() < part) h_buf.resize(part);
-    KU_HIP(DM, hipMemcpy(h_buf.data(), (const uint8_t *)d_src + at, part, hipMemcpyDeviceToHost));
-    if (!write_all(fd, h_buf.data(), part)) return fail(KU_ENOINPUT, "write error on " + path);
-    at += part;
-  }
-  return KU_OK;
-}
 
 }  // namespace
 
@@ -285,11 +206,7 @@ extern "C" int ku_db_merge_files(int device, const char *const *kdb_paths, const
 
   KU_TRY(ku_check_device(device));
   KU_HIP(DM, hipSetDevice(device));
-  if (device_bytes == 0) {  // half of what is free now
-    size_t free_b = 0, total_b = 0;
-    KU_HIP(DM, hipMemGetInfo(&free_b, &total_b));
-    device_bytes = std::max<uint64_t>(free_b / 2, KU_DBMERGE_MIN_BYTES);
-  }
+  KU_TRY(ku_default_budget(DM, KU_DBMERGE_MIN_BYTES, &device_bytes));
   const KuDbMergeBudget budget = ku_dbmerge_budget(device_bytes);
 
   // ---- chunk plan: from `lo`, the longest range of bins that holds at most `capacity` records of all inputs together and
@@ -323,38 +240,20 @@ extern "C" int ku_db_merge_files(int device, const char *const *kdb_paths, const
     lo = good;
   }
 
-  // ---- taxonomy: node universe = taxDB ids U the values of every input U {0, 1}, ascending; Parent_map as a node array
-  std::vector<uint32_t> nodes, parent;
-  if (tax) {
-    for (uint32_t i = 0; i < n_inputs; ++i) {
-      uint64_t nv = 0;
-      KU_TRY(ku_db_values(in.dbs[i], nullptr, &nv));
-      const size_t at = nodes.size();
-      nodes.resize(at + nv);
-      if (nv) KU_TRY(ku_db_values(in.dbs[i], nodes.data() + at, &nv));
-    }
-    nodes.insert(nodes.end(), tax->ids.begin(), tax->ids.end());
-    nodes.push_back(0);
-    nodes.push_back(1);
-    std::sort(nodes.begin(), nodes.end());
-    nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
-    auto node_of = [&](uint32_t t) { return (uint32_t)(std::lower_bound(nodes.begin(), nodes.end(), t) - nodes.begin()); };
-    parent.assign(nodes.size(), 0);
-    for (size_t i = 0; i < tax->ids.size(); ++i)  // Parent_map semantics: 0 = no parent pointer
-      if (tax->ids[i] != 0 && tax->parent_map[i] != 0) parent[node_of(tax->ids[i])] = node_of(tax->parent_map[i]);
-  }
+  // ---- taxonomy: the node table over the values of every input
+  KuNodeTable nodes;
+  if (tax) KU_TRY(nodes.build(tax, {in.dbs.begin(), in.dbs.end()}));
 
   // ---- device: buffers for the largest chunk of the plan (never more than the budget's capacity)
   Dev dev;
   hipStream_t s = nullptr;
   KU_HIP(DM, hipStreamCreate(&s));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+  StreamGuard sg{s};
   uint8_t *d_acc = nullptr, *d_in = nullptr, *d_out = nullptr, *d_dup = nullptr;
   uint64_t *d_off_acc = nullptr, *d_off_in = nullptr, *d_off_out = nullptr, *d_rank = nullptr, *d_before = nullptr;
   uint32_t *d_parent = nullptr, *d_node_taxid = nullptr;
   unsigned long long *d_ctl = nullptr;  // [0] error bits, [1] folded
-  void *d_tmp = nullptr;
-  size_t tmp_have = 0;
+  KuScratch tmp;
   KU_HIP(DM, dev.alloc(&d_acc, max_records * ps));
   KU_HIP(DM, dev.alloc(&d_in, max_records * ps));
   KU_HIP(DM, dev.alloc(&d_out, max_records * ps));
@@ -367,41 +266,18 @@ extern "C" int ku_db_merge_files(int device, const char *const *kdb_paths, const
   KU_HIP(DM, dev.alloc(&d_ctl, 16));
   MgFold fold{nullptr, nullptr, 0};
   if (tax) {
-    KU_HIP(DM, dev.alloc(&d_parent, parent.size() * 4));
+    KU_HIP(DM, dev.alloc(&d_parent, nodes.size() * 4));
     KU_HIP(DM, dev.alloc(&d_node_taxid, nodes.size() * 4));
-    KU_HIP(DM, hipMemcpy(d_parent, parent.data(), parent.size() * 4, hipMemcpyHostToDevice));
-    KU_HIP(DM, hipMemcpy(d_node_taxid, nodes.data(), nodes.size() * 4, hipMemcpyHostToDevice));
-    fold = MgFold{d_parent, d_node_taxid, (uint32_t)nodes.size()};
+    KU_TRY(nodes.upload(DM, s, d_parent, d_node_taxid));
+    fold = MgFold{d_parent, d_node_taxid, nodes.size()};
   }
-  auto scratch = [&](size_t bytes, void *&tmp, size_t &have) -> int {
-    if (bytes > tmp_have) {
-      KU_HIP(DM, hipStreamSynchronize(s));
-      if (d_tmp) dev.release(d_tmp);
-      d_tmp = nullptr;
-      tmp_have = 0;
-      KU_HIP(DM, dev.alloc(&d_tmp, bytes));
-      tmp_have = bytes;
-    }
-    tmp = d_tmp;
-    have = tmp_have;
-    return KU_OK;
-  };
+  auto scratch = tmp.provider(DM, s);
 
   // ---- outputs: database header of input 0 (its key count is patched at the end), index header as db_sort writes it
-  MgOutputs out;
-  out.kdb_path = out_kdb_path;
-  out.idx_path = out_idx_path;
-  out.kdb_fd = ::open(out_kdb_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (out.kdb_fd < 0) return fail(KU_ENOINPUT, std::string("can't write ") + out_kdb_path);
-  out.idx_fd = ::open(out_idx_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (out.idx_fd < 0) return fail(KU_ENOINPUT, std::string("can't write ") + out_idx_path);
-  {
-    const size_t hdr = (size_t)(in.dbs[0]->pairs - (const uint8_t *)in.dbs[0]->map_kdb);
-    if (!write_all(out.kdb_fd, in.dbs[0]->map_kdb, hdr)) return fail(KU_ENOINPUT, std::string("write error on ") + out_kdb_path);
-    const uint8_t nt8 = (uint8_t)info[0].nt;
-    if (!write_all(out.idx_fd, info[0].idx_type == 1 ? "KRAKIDX" : "KRAKIX2", 7) || !write_all(out.idx_fd, &nt8, 1))
-      return fail(KU_ENOINPUT, std::string("write error on ") + out_idx_path);
-  }
+  KuDbFiles out;
+  if (!out.open(out_kdb_path, out_idx_path) ||
+      !out.begin(in.dbs[0]->map_kdb, (size_t)(in.dbs[0]->pairs - (const uint8_t *)in.dbs[0]->map_kdb), info[0].idx_type, info[0].nt))
+    return fail(KU_ENOINPUT, out.error);
 
   ku_db_merge_stats st{};
   st.capacity = budget.capacity;
@@ -409,7 +285,7 @@ extern "C" int ku_db_merge_files(int device, const char *const *kdb_paths, const
   uint64_t key_ct = 0;
   for (size_t c = 0; c + 1 < bounds.size(); ++c) {
     const uint64_t lo = bounds[c], nb = bounds[c + 1] - lo;
-    double t0 = mg_now();
+    double t0 = ku_now();
     KU_HIP(DM, hipMemsetAsync(d_ctl, 0, 16, s));
     // the fold's left side starts as input 0's slice
     MgSide A{d_acc, d_off_acc, off[0][lo], off[0][lo + nb] - off[0][lo]};
@@ -422,8 +298,8 @@ extern "C" int ku_db_merge_files(int device, const char *const *kdb_paths, const
       if (B.n) KU_HIP(DM, hipMemcpyAsync(d_in, in.dbs[i]->pairs + B.base * ps, B.n * ps, hipMemcpyHostToDevice, s));
       KU_HIP(DM, hipMemcpyAsync(d_off_in, off[i] + lo, (nb + 1) * 8, hipMemcpyHostToDevice, s));
       KU_HIP(DM, hipStreamSynchronize(s));
-      st.upload_s += mg_now() - t0;
-      t0 = mg_now();
+      st.upload_s += ku_now() - t0;
+      t0 = ku_now();
       const uint64_t out_cap = A.n + B.n;  // <= max_records: the chunk's records of the inputs 0 .. i
       hipLaunchKernelGGL(dbmerge_rank_b_kernel, dim3(ku_grid_256(B.n)), dim3(256), 0, s, A, B, nb, key_len, d_rank, d_dup,
                          reinterpret_cast<uint32_t *>(d_ctl));
@@ -443,8 +319,8 @@ extern "C" int ku_db_merge_files(int device, const char *const *kdb_paths, const
       uint64_t dups = 0;
       KU_HIP(DM, hipMemcpyAsync(&dups, d_before + B.n, 8, hipMemcpyDeviceToHost, s));
       KU_HIP(DM, hipStreamSynchronize(s));
-      st.merge_s += mg_now() - t0;
-      t0 = mg_now();
+      st.merge_s += ku_now() - t0;
+      t0 = ku_now();
       st.duplicates += dups;
       // the result is the next step's left side
       A = MgSide{d_res, d_off_res, 0, out_cap - dups};
@@ -458,18 +334,15 @@ extern "C" int ku_db_merge_files(int device, const char *const *kdb_paths, const
       return fail(KU_EDATA, "db_merge: values differ for a k-mer present in both inputs; a taxonomy is needed to fold them");
     st.folded += ctl[1];
     // the chunk's records behind those of the chunks before, the offsets of its bins (the closing one: below)
-    KU_TRY(mg_write_from_device(out.kdb_fd, out.kdb_path, A.raw, A.n * ps, h_buf));
-    KU_TRY(mg_write_from_device(out.idx_fd, out.idx_path, A.off, nb * 8, h_buf));
+    KU_TRY(ku_append_from_device(DM, out, &KuDbFiles::append_records, A.raw, A.n * ps, h_buf));
+    KU_TRY(ku_append_from_device(DM, out, &KuDbFiles::append_offsets, A.off, nb * 8, h_buf));
     key_ct += A.n;
     st.chunks++;
-    st.write_s += mg_now() - t0;
+    st.write_s += ku_now() - t0;
   }
-  // offsets[4^nt] = key_ct (make_index, krakendb.cpp:136-139); key_ct into the header (krakendb.cpp:72)
-  const double t0 = mg_now();
-  bool ok = write_all(out.idx_fd, &key_ct, 8);
-  ok = ::pwrite(out.kdb_fd, &key_ct, 8, 48) == 8 && ok;
-  if (!ok || !out.close_both()) return fail(KU_ENOINPUT, std::string("write error on ") + out_kdb_path + " / " + out_idx_path);
-  st.write_s += mg_now() - t0;
+  const double t0 = ku_now();
+  if (!out.finish(key_ct)) return fail(KU_ENOINPUT, out.error);
+  st.write_s += ku_now() - t0;
   st.key_ct = key_ct;
   if (stats) *stats = st;
   return KU_OK;

@@ -23,16 +23,13 @@ struct Rec {  // what travels through the second sort
   uint32_t pad;
 };
 
-// records of key_len + 4 bytes -> k-mer keys and values
+// records in their on-disk form -> k-mer keys and values
 __global__ void dbsort_unpack_kernel(const uint8_t *__restrict__ raw, uint64_t n, uint32_t key_len, uint64_t *kmers,
                                      uint32_t *vals, int zero_vals) {
-  const uint64_t ps = key_len + 4;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint8_t *p = raw + i * ps;
-    uint64_t kmer = 0;
-    for (uint32_t b = 0; b < key_len; ++b) kmer |= (uint64_t)p[b] << (8 * b);
-    uint32_t v = 0;
-    for (uint32_t b = 0; b < 4; ++b) v |= (uint32_t)p[key_len + b] << (8 * b);
+    uint64_t kmer;
+    uint32_t v;
+    ku_rec_load(raw, i, key_len, kmer, v);
     kmers[i] = kmer;
     vals[i] = zero_vals ? 0u : v;  // db_sort -z (src/db_sort.cpp:103-104)
   }
@@ -52,14 +49,11 @@ __global__ void dbsort_binkey_kernel(const uint64_t *__restrict__ kmers, const u
   }
 }
 
-// sorted records -> the on-disk form (key_len little-endian key bytes, 4 value bytes)
+// sorted records -> the on-disk form
 __global__ void dbsort_pack_kernel(const Rec *__restrict__ recs, uint64_t n, uint32_t key_len, uint8_t *raw) {
-  const uint64_t ps = key_len + 4;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     const Rec r = recs[i];
-    uint8_t *p = raw + i * ps;
-    for (uint32_t b = 0; b < key_len; ++b) p[b] = (uint8_t)(r.kmer >> (8 * b));
-    for (uint32_t b = 0; b < 4; ++b) p[key_len + b] = (uint8_t)(r.val >> (8 * b));
+    ku_rec_store(raw, i, key_len, r.kmer, r.val);
   }
 }
 
@@ -74,6 +68,14 @@ auto ds_scratch(Dev &dev, void *&d_tmp) {
 }
 
 }  // namespace
+
+// the first step of db_sort and of ku_setlcas_open (ku_build.h)
+int dbsort_unpack(const KuHipWho &who, hipStream_t s, const uint8_t *d_raw, uint64_t n, uint32_t key_len, uint64_t *d_kmer,
+                  uint32_t *d_val, bool zero_vals) {
+  hipLaunchKernelGGL(dbsort_unpack_kernel, dim3(ku_grid_256(n)), dim3(256), 0, s, d_raw, n, key_len, d_kmer, d_val, (int)zero_vals);
+  KU_HIP(who, hipGetLastError());
+  return KU_OK;
+}
 
 // the second half of db_sort (ku_build.h says what goes in and what comes out)
 int dbsort_bin_order_and_pack(Dev &dev, hipStream_t s, uint64_t *d_kmer, uint32_t *d_val, bool release_inputs, uint64_t n,
@@ -154,18 +156,16 @@ extern "C" int ku_db_sort_files(int device, const char *in_path, const char *out
   Dev dev;
   hipStream_t s = nullptr;
   KU_HIP(DS, hipStreamCreate(&s));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+  StreamGuard sg{s};
   uint8_t *d_raw = nullptr;
   uint64_t *d_kmer_a = nullptr, *d_kmer_b = nullptr, *d_off = nullptr;
   uint32_t *d_val_a = nullptr, *d_val_b = nullptr;
   void *d_tmp = nullptr;
-  const unsigned grid = ku_grid_256(n);
   KU_HIP(DS, dev.alloc(&d_raw, n * ps));
   KU_HIP(DS, dev.alloc(&d_kmer_a, n * 8));
   KU_HIP(DS, dev.alloc(&d_val_a, n * 4));
   if (n) KU_HIP(DS, hipMemcpyAsync(d_raw, in + hdr, n * ps, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(dbsort_unpack_kernel, dim3(grid), dim3(256), 0, s, d_raw, n, key_len, d_kmer_a, d_val_a, zero_vals);
-  KU_HIP(DS, hipGetLastError());
+  KU_TRY(dbsort_unpack(DS, s, d_raw, n, key_len, d_kmer_a, d_val_a, zero_vals != 0));
   // pass 1: by k-mer (2k significant bits)
   KU_HIP(DS, dev.alloc(&d_kmer_b, n * 8));
   KU_HIP(DS, dev.alloc(&d_val_b, n * 4));
@@ -183,20 +183,12 @@ extern "C" int ku_db_sort_files(int device, const char *in_path, const char *out
   }
 
   // ---- outputs: header copied verbatim (src/db_sort.cpp:56-75), then the sorted records; KRAKIX2 index
-  std::vector<uint8_t> h_raw(n * ps);
-  std::vector<uint64_t> h_off(n_bins + 1);
-  if (n) KU_HIP(DS, hipMemcpy(h_raw.data(), d_raw, n * ps, hipMemcpyDeviceToHost));
-  KU_HIP(DS, hipMemcpy(h_off.data(), d_off, (n_bins + 1) * 8, hipMemcpyDeviceToHost));
-  int ofd = ::open(out_kdb_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (ofd < 0) return fail(KU_ENOINPUT, std::string("can't write ") + out_kdb_path);
-  bool ok = write_all(ofd, in, hdr) && write_all(ofd, h_raw.data(), h_raw.size());
-  ok = (::close(ofd) == 0) && ok;
-  if (!ok) return fail(KU_ENOINPUT, std::string("write error on ") + out_kdb_path);
-  ofd = ::open(out_idx_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (ofd < 0) return fail(KU_ENOINPUT, std::string("can't write ") + out_idx_path);
-  const uint8_t nt8 = (uint8_t)nt;
-  ok = write_all(ofd, "KRAKIX2", 7) && write_all(ofd, &nt8, 1) && write_all(ofd, h_off.data(), h_off.size() * 8);
-  ok = (::close(ofd) == 0) && ok;
-  if (!ok) return fail(KU_ENOINPUT, std::string("write error on ") + out_idx_path);
+  // (key_ct at byte 48 is written once more with the value it has; the closing offset is d_off[n_bins])
+  KuDbFiles out;
+  std::vector<uint8_t> h_buf;
+  if (!out.open(out_kdb_path, out_idx_path) || !out.begin(in, hdr, 2, nt)) return fail(KU_ENOINPUT, out.error);
+  KU_TRY(ku_append_from_device(DS, out, &KuDbFiles::append_records, d_raw, n * ps, h_buf));
+  KU_TRY(ku_append_from_device(DS, out, &KuDbFiles::append_offsets, d_off, n_bins * 8, h_buf));
+  if (!out.finish(n)) return fail(KU_ENOINPUT, out.error);
   return KU_OK;
 }

@@ -1,7 +1,8 @@
 // ku_kmerdb.h -- device helpers of the k-mer set builder (ku_kmerdb_*, bin/kmer_db; entry points and the extraction
-// kernel in ku_kmerdb.hip): the minimizer bin key shared with db_sort's second half (ku_dbsort.hip), and the tile decoding
-// that turns sequence bytes into k-mers, shared with the sketch kernel (ku_sketch.hip).  Helpers, constants and argument
-// structs only: a kernel lives in the one .hip file that launches it.
+// kernel in ku_kmerdb.hip) and of the other build tools: the minimizer bin key (db_sort's second half, set_lcas), the on-disk
+// record codec (db_sort, db_merge), the taxid -> node lookup (set_lcas, db_merge), and the tile decoding that turns sequence
+// bytes into k-mers, shared with the sketch kernel (ku_sketch.hip).  Helpers, constants and argument structs only: a kernel
+// lives in the one .hip file that launches it.
 #pragma once
 #include "ku_device.h"
 
@@ -17,6 +18,55 @@ __device__ __forceinline__ uint32_t ku_bin_key(uint64_t canon, uint32_t k, uint3
     best = v < best ? v : best;
   }
   return best;
+}
+
+// ---- the on-disk record of a database: key_len little-endian key bytes + 4 value bytes, record i at raw + i * (key_len + 4).
+// At key_len 8 a record is three aligned dwords; other lengths go byte by byte.
+struct __attribute__((packed, aligned(4))) KuKey8 { uint32_t lo, hi; };
+struct __attribute__((packed, aligned(4))) KuRec12 { uint32_t lo, hi, val; };
+
+__device__ __forceinline__ uint64_t ku_rec_key(const uint8_t *__restrict__ raw, uint64_t i, uint32_t key_len) {
+  if (key_len == 8) {
+    const KuKey8 r = *reinterpret_cast<const KuKey8 *>(raw + i * 12);
+    return (uint64_t)r.hi << 32 | r.lo;
+  }
+  const uint8_t *p = raw + i * (key_len + 4);
+  uint64_t key = 0;
+  for (uint32_t b = 0; b < key_len; ++b) key |= (uint64_t)p[b] << (8 * b);
+  return key;
+}
+__device__ __forceinline__ void ku_rec_load(const uint8_t *__restrict__ raw, uint64_t i, uint32_t key_len, uint64_t &key, uint32_t &val) {
+  if (key_len == 8) {
+    const KuRec12 r = *reinterpret_cast<const KuRec12 *>(raw + i * 12);
+    key = (uint64_t)r.hi << 32 | r.lo;
+    val = r.val;
+    return;
+  }
+  const uint8_t *p = raw + i * (key_len + 4);
+  key = 0;
+  val = 0;
+  for (uint32_t b = 0; b < key_len; ++b) key |= (uint64_t)p[b] << (8 * b);
+  for (uint32_t b = 0; b < 4; ++b) val |= (uint32_t)p[key_len + b] << (8 * b);
+}
+__device__ __forceinline__ void ku_rec_store(uint8_t *raw, uint64_t i, uint32_t key_len, uint64_t key, uint32_t val) {
+  if (key_len == 8) {
+    *reinterpret_cast<KuRec12 *>(raw + i * 12) = KuRec12{(uint32_t)key, (uint32_t)(key >> 32), val};
+    return;
+  }
+  uint8_t *p = raw + i * (key_len + 4);
+  for (uint32_t b = 0; b < key_len; ++b) p[b] = (uint8_t)(key >> (8 * b));
+  for (uint32_t b = 0; b < 4; ++b) p[key_len + b] = (uint8_t)(val >> (8 * b));
+}
+
+// taxid -> node: the lower bound of the taxid in the ascending node universe (KuNodeTable, ku_build.h), n_nodes where
+// every node's taxid is below it
+__device__ __forceinline__ uint32_t ku_node_of(const uint32_t *__restrict__ node_taxid, uint32_t n_nodes, uint32_t taxid) {
+  uint32_t lo = 0, hi = n_nodes;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (node_taxid[mid] < taxid) lo = mid + 1; else hi = mid;
+  }
+  return lo;
 }
 
 // One wave scans a tile of KMD_TILE consecutive windows: its 64 lanes load 16 sequence bytes each (plus the two chunks the

@@ -6,7 +6,6 @@
 // front of the same buffer.  ku_kmerdb_end_pass hands the set to dbsort_bin_order_and_pack (ku_dbsort.hip) and appends its
 // records and its part of the index to the files.  (ku_sketch_*, ku_sketch.hip, estimates beforehand how many passes a
 // library needs.)  The budget rule is ku_kmerdb_budget (ku_kmerdb_budget.h).  Offline tool, not on the classify hot path.
-#include <chrono>
 #include <cstring>  // (rocPRIM uses memset without including it)
 
 #include <rocprim/rocprim.hpp>
@@ -74,14 +73,12 @@ struct ku_kmerdb {
   uint32_t pass = 0;  // passes ended
   bool finished = false, failed = false;
   uint64_t n_bins = 0, cap = 0, usable = 0, seg_bytes = 0;  // cap, usable, seg_bytes: ku_kmerdb_budget
-  std::string kdb_path, idx_path;
-  int kdb_fd = -1, idx_fd = -1;
+  KuDbFiles out;  // removed by its destructor unless ku_kmerdb_finish got to its end
   hipStream_t stream = nullptr;
   uint64_t *d_a = nullptr, *d_b = nullptr;  // d_a: the distinct set [0, n_set), then the candidates [n_set, fill)
   uint8_t *d_seq = nullptr;
   unsigned long long *d_ctl = nullptr;      // [0] the buffer's cursor, [1] rocPRIM's unique count, [2] the kernel's error word
-  void *d_tmp = nullptr;
-  size_t tmp_bytes = 0;
+  KuScratch tmp;  // rocPRIM's
   uint64_t n_set = 0, fill = 0, key_ct = 0;
   uint64_t merge_piece = 0;  // keys of either input per rocprim::merge call (kmd_merge)
   uint64_t merge_calls = 0;  // of the running pass
@@ -92,8 +89,6 @@ struct ku_kmerdb {
 
 namespace {
 
-constexpr size_t KMD_IO_CHUNK = (size_t)32 << 20;
-
 KuHipWho KMD(ku_kmerdb *h) { return {"kmer_db: ", " (a smaller -s, or more passes: -P)", &h->failed}; }
 
 int kmd_fail(ku_kmerdb *h, int code, const std::string &msg) {
@@ -101,35 +96,13 @@ int kmd_fail(ku_kmerdb *h, int code, const std::string &msg) {
   return fail(code, msg);
 }
 
-double kmd_now() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 // bins of pass p: [p * 4^nt / n_passes, (p + 1) * 4^nt / n_passes)
 uint64_t kmd_pass_bound(const ku_kmerdb *h, uint32_t p) { return (uint64_t)p * h->n_bins / h->n_passes; }
 
 }  // namespace
 
-static int kmd_reserve_tmp(ku_kmerdb *h, size_t bytes) {
-  if (bytes <= h->tmp_bytes) return KU_OK;
-  KU_HIP(KMD(h), hipStreamSynchronize(h->stream));
-  if (h->d_tmp) (void)hipFree(h->d_tmp);
-  h->d_tmp = nullptr;
-  h->tmp_bytes = 0;
-  KU_HIP(KMD(h), hipMalloc(&h->d_tmp, bytes));
-  h->tmp_bytes = bytes;
-  return KU_OK;
-}
-
-// rocPRIM's scratch (ku_rocprim): the handle's buffer, grown when the call needs more, handed over whole
-static auto kmd_scratch(ku_kmerdb *h) {
-  return [h](size_t need, void *&tmp, size_t &have) -> int {
-    KU_TRY(kmd_reserve_tmp(h, need));
-    tmp = h->d_tmp;
-    have = h->tmp_bytes;
-    return KU_OK;
-  };
-}
+// rocPRIM's scratch (ku_rocprim): the handle's buffer
+static auto kmd_scratch(ku_kmerdb *h) { return h->tmp.provider(KMD(h), h->stream); }
 
 // first index in the sorted device array [0, n) whose key is not below `key` (host-driven: one 8-byte copy per step; used for
 // the few cut points of kmd_merge only)
@@ -196,7 +169,7 @@ static int kmd_merge(ku_kmerdb *h, const uint64_t *a, uint64_t na, const uint64_
 static int kmd_flush(ku_kmerdb *h) {
   const uint64_t m = h->fill - h->n_set;
   if (m == 0) return KU_OK;
-  const double t0 = kmd_now();
+  const double t0 = ku_now();
   hipStream_t s = h->stream;
   uint64_t *a_side = h->d_a + h->n_set, *b_side = h->d_b + h->n_set;
   rocprim::double_buffer<uint64_t> keys(a_side, b_side);
@@ -230,7 +203,7 @@ static int kmd_flush(ku_kmerdb *h) {
   KU_HIP(KMD(h), hipMemcpyAsync(h->d_ctl, &cur, 8, hipMemcpyHostToDevice, s));
   KU_HIP(KMD(h), hipStreamSynchronize(s));
   h->flushes++;
-  h->stats.flush_s += kmd_now() - t0;
+  h->stats.flush_s += ku_now() - t0;
   if (h->n_set > h->usable)
     return kmd_fail(h, KU_ENOMEM, "kmer_db: the distinct k-mers of pass " + std::to_string(h->pass + 1) + " (" + std::to_string(h->n_set) +
                                       " so far) do not fit the device budget (" + std::to_string(h->cap) +
@@ -238,13 +211,10 @@ static int kmd_flush(ku_kmerdb *h) {
   return KU_OK;
 }
 
-static int kmd_open_impl(ku_kmerdb *h, uint64_t device_bytes) {
+static int kmd_open_impl(ku_kmerdb *h, uint64_t device_bytes, const char *kdb_path, const char *idx_path) {
   KU_HIP(KMD(h), hipSetDevice(h->device));
-  if (device_bytes == 0) {  // half of what is free now: the rest is end_pass's (56 bytes per distinct k-mer of the pass)
-    size_t free_b = 0, total_b = 0;
-    KU_HIP(KMD(h), hipMemGetInfo(&free_b, &total_b));
-    device_bytes = free_b / 2;
-  }
+  // (the default leaves the other half to end_pass: 56 bytes per distinct k-mer of the pass)
+  KU_TRY(ku_default_budget(KMD(h), KU_KMERDB_MIN_BYTES, &device_bytes));
   if (device_bytes < KU_KMERDB_MIN_BYTES) return kmd_fail(h, KU_EINVAL, "kmer_db: the device budget is below the minimum of 64 KiB");
   const KuKmerdbBudget budget = ku_kmerdb_budget(device_bytes);
   h->seg_bytes = budget.segment;
@@ -252,19 +222,9 @@ static int kmd_open_impl(ku_kmerdb *h, uint64_t device_bytes) {
   h->usable = budget.usable;
   h->merge_piece = std::min<uint64_t>((uint64_t)1 << 30, std::max<uint64_t>(h->cap / 4, 1024));
   // ---- outputs: both files exist (and are writable) before any work is done
-  h->kdb_fd = ::open(h->kdb_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (h->kdb_fd < 0) return kmd_fail(h, KU_ENOINPUT, "can't write " + h->kdb_path);
-  h->idx_fd = ::open(h->idx_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (h->idx_fd < 0) return kmd_fail(h, KU_ENOINPUT, "can't write " + h->idx_path);
-  // Jellyfish-1 list header as KrakenDB reads it (krakendb.cpp:60-78,177): key_ct is patched in by ku_kmerdb_finish
-  const uint64_t key_bits = 2ull * h->k, val_len = 4;
-  std::vector<uint8_t> hdr(72 + 2 * (4 + 8 * key_bits), 0);
-  memcpy(hdr.data(), "JFLISTDN", 8);
-  memcpy(hdr.data() + 8, &key_bits, 8);
-  memcpy(hdr.data() + 16, &val_len, 8);
-  const uint8_t nt8 = (uint8_t)h->nt;
-  if (!write_all(h->kdb_fd, hdr.data(), hdr.size())) return kmd_fail(h, KU_ENOINPUT, "write error on " + h->kdb_path);
-  if (!write_all(h->idx_fd, "KRAKIX2", 7) || !write_all(h->idx_fd, &nt8, 1)) return kmd_fail(h, KU_ENOINPUT, "write error on " + h->idx_path);
+  // (the list header's key_ct is patched in by ku_kmerdb_finish)
+  const std::vector<uint8_t> hdr = ku_jflist_header(2ull * h->k);
+  if (!h->out.open(kdb_path, idx_path) || !h->out.begin(hdr.data(), hdr.size(), 2, h->nt)) return kmd_fail(h, KU_ENOINPUT, h->out.error);
   // ---- device
   KU_HIP(KMD(h), hipStreamCreate(&h->stream));
   KU_HIP(KMD(h), hipMalloc((void **)&h->d_a, h->cap * 8));
@@ -293,9 +253,7 @@ extern "C" int ku_kmerdb_open(int device, uint32_t k, uint32_t nt, uint32_t n_pa
   h->n_passes = n_passes;
   h->key_len = (2 * k + 7) / 8;
   h->n_bins = 1ull << (2 * nt);
-  h->kdb_path = out_kdb_path;
-  h->idx_path = out_idx_path;
-  const int st = kmd_open_impl(h, device_bytes);
+  const int st = kmd_open_impl(h, device_bytes, out_kdb_path, out_idx_path);
   if (st != KU_OK) { ku_kmerdb_close(h); return st; }
   *out = h;
   return KU_OK;
@@ -305,13 +263,10 @@ extern "C" void ku_kmerdb_close(ku_kmerdb *h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void *p : {(void *)h->d_a, (void *)h->d_b, (void *)h->d_seq, (void *)h->d_ctl, h->d_tmp})
+  for (void *p : {(void *)h->d_a, (void *)h->d_b, (void *)h->d_seq, (void *)h->d_ctl})
     if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  // files of a build that did not reach the end of ku_kmerdb_finish are not databases: none is left behind
-  if (h->kdb_fd >= 0) { ::close(h->kdb_fd); ::unlink(h->kdb_path.c_str()); }
-  if (h->idx_fd >= 0) { ::close(h->idx_fd); ::unlink(h->idx_path.c_str()); }
-  delete h;
+  delete h;  // (frees rocPRIM's scratch; files of a build that did not reach the end of ku_kmerdb_finish go with h->out)
 }
 
 extern "C" int ku_kmerdb_add(ku_kmerdb *h, const char *seq, uint64_t len) {
@@ -320,7 +275,7 @@ extern "C" int ku_kmerdb_add(ku_kmerdb *h, const char *seq, uint64_t len) {
   if (h->finished || h->pass >= h->n_passes) return fail(KU_EINVAL, "ku_kmerdb_add: every pass has been ended");
   if (len < h->k) return KU_OK;
   KU_HIP(KMD(h), hipSetDevice(h->device));
-  const double t0 = kmd_now(), flush_s0 = h->stats.flush_s;
+  const double t0 = ku_now(), flush_s0 = h->stats.flush_s;
   hipStream_t s = h->stream;
   const uint32_t k = h->k;
   KmdScan a{};
@@ -366,7 +321,7 @@ extern "C" int ku_kmerdb_add(ku_kmerdb *h, const char *seq, uint64_t len) {
     if (pos + seg_len == len) break;
     pos += n_win;
   }
-  h->stats.scan_s += (kmd_now() - t0) - (h->stats.flush_s - flush_s0);  // upload + extraction: the flushes are counted apart
+  h->stats.scan_s += (ku_now() - t0) - (h->stats.flush_s - flush_s0);  // upload + extraction: the flushes are counted apart
   return KU_OK;
 }
 
@@ -376,7 +331,7 @@ extern "C" int ku_kmerdb_end_pass(ku_kmerdb *h) {
   if (h->finished || h->pass >= h->n_passes) return fail(KU_EINVAL, "ku_kmerdb_end_pass: every pass has been ended");
   KU_HIP(KMD(h), hipSetDevice(h->device));
   if (int st = kmd_flush(h)) return st;
-  const double t0 = kmd_now();
+  const double t0 = ku_now();
   hipStream_t s = h->stream;
   const uint64_t n = h->n_set, ps = h->key_len + 4;
   const uint64_t bin_lo = kmd_pass_bound(h, h->pass), n_hist = kmd_pass_bound(h, h->pass + 1) - bin_lo;
@@ -402,19 +357,9 @@ extern "C" int ku_kmerdb_end_pass(ku_kmerdb *h) {
       if (st == KU_ENOMEM) ku_set_error(std::string(ku_last_error()) + " -- kmer_db: use more passes (-P)");
       return st;
     }
-    h->h_buf.resize(KMD_IO_CHUNK);
-    for (uint64_t at = 0, total = n * ps; at < total;) {  // the pass's records, behind those of the passes before
-      const size_t part = (size_t)std::min<uint64_t>(KMD_IO_CHUNK, total - at);
-      KU_HIP(KMD(h), hipMemcpy(h->h_buf.data(), d_raw + at, part, hipMemcpyDeviceToHost));
-      if (!write_all(h->kdb_fd, h->h_buf.data(), part)) return kmd_fail(h, KU_ENOINPUT, "write error on " + h->kdb_path);
-      at += part;
-    }
-    for (uint64_t at = 0, total = n_hist * 8; at < total;) {  // offsets of the pass's bins (the closing one: ku_kmerdb_finish)
-      const size_t part = (size_t)std::min<uint64_t>(KMD_IO_CHUNK, total - at);
-      KU_HIP(KMD(h), hipMemcpy(h->h_buf.data(), (const uint8_t *)d_off + at, part, hipMemcpyDeviceToHost));
-      if (!write_all(h->idx_fd, h->h_buf.data(), part)) return kmd_fail(h, KU_ENOINPUT, "write error on " + h->idx_path);
-      at += part;
-    }
+    // the pass's records behind those of the passes before; the offsets of its bins (the closing one: ku_kmerdb_finish)
+    KU_TRY(ku_append_from_device(KMD(h), h->out, &KuDbFiles::append_records, d_raw, n * ps, h->h_buf));
+    KU_TRY(ku_append_from_device(KMD(h), h->out, &KuDbFiles::append_offsets, d_off, n_hist * 8, h->h_buf));
   }
   h->key_ct += n;
   h->stats.windows = h->windows;
@@ -431,7 +376,7 @@ extern "C" int ku_kmerdb_end_pass(ku_kmerdb *h) {
   KU_HIP(KMD(h), hipMemsetAsync(h->d_ctl, 0, 3 * 8, s));
   KU_HIP(KMD(h), hipStreamSynchronize(s));
   if (!h->d_b && h->pass < h->n_passes) KU_HIP(KMD(h), hipMalloc((void **)&h->d_b, h->cap * 8));
-  h->stats.end_pass_s += kmd_now() - t0;
+  h->stats.end_pass_s += ku_now() - t0;
   return KU_OK;
 }
 
@@ -448,15 +393,7 @@ extern "C" int ku_kmerdb_finish(ku_kmerdb *h, uint64_t *key_ct) {
   if (h->pass < h->n_passes)
     return fail(KU_EINVAL, "ku_kmerdb_finish: " + std::to_string(h->n_passes - h->pass) + " of " + std::to_string(h->n_passes) + " passes have not been ended");
   if (h->key_ct == 0) return kmd_fail(h, KU_EDATA, "kmer_db: no k-mers in the input");  // (ku_kmerdb_close removes the files)
-  // offsets[4^nt] = key_ct (make_index, krakendb.cpp:136-139); key_ct into the header (krakendb.cpp:72)
-  bool ok = write_all(h->idx_fd, &h->key_ct, 8);
-  ok = (::close(h->idx_fd) == 0) && ok;
-  h->idx_fd = -1;
-  if (!ok) { ::unlink(h->idx_path.c_str()); return kmd_fail(h, KU_ENOINPUT, "write error on " + h->idx_path); }
-  ok = ::pwrite(h->kdb_fd, &h->key_ct, 8, 48) == 8;
-  ok = (::close(h->kdb_fd) == 0) && ok;
-  h->kdb_fd = -1;
-  if (!ok) { ::unlink(h->kdb_path.c_str()); ::unlink(h->idx_path.c_str()); return kmd_fail(h, KU_ENOINPUT, "write error on " + h->kdb_path); }
+  if (!h->out.finish(h->key_ct)) return kmd_fail(h, KU_ENOINPUT, h->out.error);
   h->finished = true;
   if (key_ct) *key_ct = h->key_ct;
   return KU_OK;

@@ -33,8 +33,7 @@ struct SlDev {
 #define KU_SL_NOWHERE (~0ull)
 __global__ void setlcas_kernel(SlDev d, const uint8_t *__restrict__ seq, uint64_t len, uint32_t node, uint32_t mode,
                                uint32_t contam_code, unsigned long long *n_missing, unsigned long long *where) {
-  const uint32_t k = d.k, m = d.nt, w = k - m + 1;
-  const uint32_t mmask = (uint32_t)((1ull << (2 * m)) - 1);
+  const uint32_t k = d.k;
   const uint64_t n = len >= k ? len - k + 1 : 0;
   for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t fwd = 0;
@@ -47,13 +46,7 @@ __global__ void setlcas_kernel(SlDev d, const uint8_t *__restrict__ seq, uint64_
     if (amb) { if (mode == 3) where[p] = KU_SL_NOWHERE; continue; }
     const uint64_t rc = ku_revcomp64(fwd, k);
     const uint64_t canon = fwd < rc ? fwd : rc;
-    uint32_t bin = 0xFFFFFFFFu;
-    for (uint32_t j = 0; j < w; ++j) {
-      const uint32_t mm = (uint32_t)(canon >> (2 * j)) & mmask;
-      const uint32_t mrc = ku_revcomp32(mm, m);
-      const uint32_t v = (mm < mrc ? mm : mrc) ^ d.xor_mask;
-      bin = v < bin ? v : bin;
-    }
+    const uint32_t bin = ku_bin_key(canon, k, d.nt, d.xor_mask);
     uint64_t lo = d.offsets[bin], hi = d.offsets[bin + 1];
     bool found = false;
     while (lo < hi) {
@@ -81,32 +74,13 @@ __global__ void setlcas_kernel(SlDev d, const uint8_t *__restrict__ seq, uint64_
   }
 }
 
-__global__ void setlcas_unpack_kernel(const uint8_t *__restrict__ raw, uint64_t n, uint32_t key_len, uint64_t *kmers,
-                                      uint32_t *vals) {
-  const uint64_t ps = key_len + 4;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint8_t *p = raw + i * ps;
-    uint64_t kmer = 0;
-    for (uint32_t b = 0; b < key_len; ++b) kmer |= (uint64_t)p[b] << (8 * b);
-    uint32_t v = 0;
-    for (uint32_t b = 0; b < 4; ++b) v |= (uint32_t)p[key_len + b] << (8 * b);
-    kmers[i] = kmer;
-    vals[i] = v;
-  }
-}
-
 // taxid <-> node through the sorted node_taxid table; with `contam` set, values that already are a contaminant taxid
 // are pinned (src/set_lcas.cpp:465-466 "keep value")
 __global__ void setlcas_to_nodes_kernel(uint32_t *vals, uint64_t n, const uint32_t *__restrict__ node_taxid,
                                         uint32_t n_nodes, uint32_t *contam) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t v = vals[i];
-    uint32_t lo = 0, hi = n_nodes;
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (node_taxid[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    vals[i] = lo;  // the node universe contains every database value
+    vals[i] = ku_node_of(node_taxid, n_nodes, v);  // the node universe contains every database value
     if (contam) contam[i] = v == TID_CONTAMINANT1 ? 0u : (v == TID_CONTAMINANT2 ? 1u : NO_CONTAM);
   }
 }
@@ -127,7 +101,7 @@ struct ku_setlcas {
   hipStream_t stream = nullptr;
   uint64_t key_ct = 0;
   uint32_t order = 0;  // sequences added so far (file order decides between contaminants)
-  std::vector<uint32_t> node_taxid;
+  KuNodeTable nodes;  // over the taxonomy and the database's values
   uint64_t *d_kmers = nullptr, *d_offsets = nullptr;
   uint32_t *d_nodes = nullptr, *d_contam = nullptr, *d_parent = nullptr, *d_node_taxid = nullptr;
   unsigned long long *d_missing = nullptr;
@@ -165,52 +139,30 @@ static int setlcas_open_impl(ku_setlcas *s, const ku_db *db, const ku_tax *tax) 
   const uint8_t *pairs = nullptr;
   const uint64_t *offsets = nullptr;
   if (ku_db_raw(db, &pairs, &offsets) != KU_OK) return KU_EINVAL;
-  // node universe: taxDB ids U database values U {0, 1}, ascending (node 0 = taxid 0, node 1 = taxid 1)
-  uint64_t nv = 0;
-  if (ku_db_values(db, nullptr, &nv) != KU_OK) return KU_EINVAL;
-  std::vector<uint32_t> nodes(nv + 1);
-  uint64_t cap = nv;
-  if (nv && ku_db_values(db, nodes.data(), &cap) != KU_OK) return KU_EINVAL;
-  nodes.resize(cap);
-  const std::vector<uint32_t> &ids = tax->ids, &parents = tax->parent_map;  // Parent_map values: 0 = no parent pointer
-  const uint64_t nt_ids = ids.size();
-  nodes.insert(nodes.end(), ids.begin(), ids.end());
-  nodes.push_back(0);
-  nodes.push_back(1);
-  std::sort(nodes.begin(), nodes.end());
-  nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
-  auto node_of = [&](uint32_t t) { return (uint32_t)(std::lower_bound(nodes.begin(), nodes.end(), t) - nodes.begin()); };
-  std::vector<uint32_t> parent(nodes.size(), 0);
-  for (uint64_t i = 0; i < nt_ids; ++i)  // Parent_map semantics: 0 = no parent pointer
-    if (ids[i] != 0 && parents[i] != 0) parent[node_of(ids[i])] = node_of(parents[i]);
-  s->node_taxid = nodes;
+  KU_TRY(s->nodes.build(tax, {db}));
+  const KuNodeTable &nodes = s->nodes;
 
   uint8_t *d_raw = nullptr;
   KU_HIP(SL, hipMalloc((void **)&s->d_kmers, std::max<uint64_t>(n, 1) * 8));
   KU_HIP(SL, hipMalloc((void **)&s->d_nodes, std::max<uint64_t>(n, 1) * 4));
   KU_HIP(SL, hipMalloc((void **)&s->d_offsets, (n_bins + 1) * 8));
-  KU_HIP(SL, hipMalloc((void **)&s->d_parent, parent.size() * 4));
+  KU_HIP(SL, hipMalloc((void **)&s->d_parent, nodes.size() * 4));
   KU_HIP(SL, hipMalloc((void **)&s->d_node_taxid, nodes.size() * 4));
   KU_HIP(SL, hipMalloc((void **)&s->d_missing, 8));
   if (s->flags & KU_SL_FORCE_CONTAMINANT) KU_HIP(SL, hipMalloc((void **)&s->d_contam, std::max<uint64_t>(n, 1) * 4));
-  KU_HIP(SL, hipMalloc((void **)&d_raw, std::max<uint64_t>(n * ps, 1)));
+  Dev dev;  // the records, here until they are unpacked
+  KU_HIP(SL, dev.alloc(&d_raw, n * ps));
   hipStream_t st = s->stream;
-  hipError_t e = hipSuccess;
-  if (n) e = hipMemcpyAsync(d_raw, pairs, n * ps, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(s->d_offsets, offsets, (n_bins + 1) * 8, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(s->d_parent, parent.data(), parent.size() * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(s->d_node_taxid, nodes.data(), nodes.size() * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(s->d_missing, 0, 8, st);
-  const unsigned grid = ku_grid_256(n);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(setlcas_unpack_kernel, dim3(grid), dim3(256), 0, st, d_raw, n, info.key_len, s->d_kmers, s->d_nodes);
-    hipLaunchKernelGGL(setlcas_to_nodes_kernel, dim3(grid), dim3(256), 0, st, s->d_nodes, n, s->d_node_taxid,
-                       (uint32_t)nodes.size(), s->d_contam);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(d_raw);
-  KU_HIP(SL, e);
+  if (n) KU_HIP(SL, hipMemcpyAsync(d_raw, pairs, n * ps, hipMemcpyHostToDevice, st));
+  KU_HIP(SL, hipMemcpyAsync(s->d_offsets, offsets, (n_bins + 1) * 8, hipMemcpyHostToDevice, st));
+  KU_TRY(nodes.upload(SL, st, s->d_parent, s->d_node_taxid));
+  KU_HIP(SL, hipMemsetAsync(s->d_missing, 0, 8, st));
+  KU_TRY(dbsort_unpack(SL, st, d_raw, n, info.key_len, s->d_kmers, s->d_nodes, /*zero_vals=*/false));
+  hipLaunchKernelGGL(setlcas_to_nodes_kernel, dim3(ku_grid_256(n)), dim3(256), 0, st, s->d_nodes, n, s->d_node_taxid, nodes.size(),
+                     s->d_contam);
+  KU_HIP(SL, hipGetLastError());
+  KU_HIP(SL, hipStreamSynchronize(st));
+  dev.release(d_raw);
   s->dev = SlDev{s->d_kmers, s->d_nodes, s->d_contam, s->d_offsets, s->d_parent, info.k, info.nt,
                  info.idx_type == 1 ? 0u : ku_index2_xor_mask(info.nt)};
   if (s->flags & KU_SL_UIDS) {  // the values as they are in the file (UIDs of an earlier run would need that run's map: uid_mapping exits on them)
@@ -238,10 +190,9 @@ extern "C" int ku_setlcas_add(ku_setlcas *s, const char *seq, uint64_t len, uint
   KU_HIP(SL, hipSetDevice(s->device));
   s->order++;
   if (len < s->dev.k) return KU_OK;
-  const auto it = std::lower_bound(s->node_taxid.begin(), s->node_taxid.end(), taxid);
-  if (it == s->node_taxid.end() || *it != taxid)
+  if (!s->nodes.has(taxid))
     return fail(KU_EINVAL, "ku_setlcas_add: taxid " + std::to_string(taxid) + " is neither in the taxonomy nor a database value");
-  const uint32_t node = (uint32_t)(it - s->node_taxid.begin());
+  const uint32_t node = s->nodes.node_of(taxid);
   if (len > s->seq_cap) {
     KU_HIP(SL, hipStreamSynchronize(s->stream));
     if (s->d_seq) (void)hipFree(s->d_seq);
@@ -356,7 +307,7 @@ extern "C" int ku_setlcas_finish(ku_setlcas *s, uint32_t *values_out, uint64_t *
   if (n_missing) *n_missing = miss;
   // back to nodes, so that further sequences can be added after a snapshot
   hipLaunchKernelGGL(setlcas_to_nodes_kernel, dim3(grid), dim3(256), 0, s->stream, s->d_nodes, n, s->d_node_taxid,
-                     (uint32_t)s->node_taxid.size(), (uint32_t *)nullptr);
+                     s->nodes.size(), (uint32_t *)nullptr);
   KU_HIP(SL, hipGetLastError());
   KU_HIP(SL, hipStreamSynchronize(s->stream));
   return KU_OK;

@@ -71,3 +71,10 @@ def test_errors(tmp_path):
         capi.db_sort_files(str(tmp_path / "missing"), str(tmp_path / "o.kdb"), str(tmp_path / "o.idx"), 7)
     with pytest.raises(capi.KuError):
         capi.db_sort_files(f"{G}/f1/database.kdb", str(tmp_path / "o.kdb"), str(tmp_path / "o.idx"), 16)
+    assert not os.path.exists(tmp_path / "o.kdb") and not os.path.exists(tmp_path / "o.idx")
+    # an output that cannot be written (the index path is a directory): KU_ENOINPUT, and no partial output is left behind
+    (tmp_path / "dir.idx").mkdir()
+    with pytest.raises(capi.KuError) as e:
+        capi.db_sort_files(f"{G}/f1/database.kdb", str(tmp_path / "o.kdb"), str(tmp_path / "dir.idx"), 7)
+    assert e.value.status == -3 and "can't write" in str(e.value)
+    assert not os.path.exists(tmp_path / "o.kdb") and os.listdir(tmp_path / "dir.idx") == []
