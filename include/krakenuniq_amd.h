@@ -582,7 +582,9 @@ int ku_counts_dims_get(ku_ctx *ctx, ku_counts_dims *out);
 int ku_counts_export(ku_ctx *ctx, uint32_t *slot_taxid, uint64_t *n_kmers, uint8_t *registers,
                      uint32_t *node_taxid, uint64_t *n_reads);
 /* Device pointers of the live state for in-place RCCL reduction at the end of a
- * sharded run (max on registers, sum on the counters). */
+ * sharded run (max on registers, sum on the counters).  Writers may only RAISE registers: the fused classify kernel keeps
+ * a floor per slot, a lower bound of the slot's 4096 registers that only ku_ctx_reset_counts clears, and drops inserts
+ * whose rank does not exceed it (env KU_HLL_FLOOR_EVERY: reads of a wave between two refreshes of a floor, 0 = no filter). */
 int ku_counts_device_ptrs(ku_ctx *ctx, uint8_t **d_registers, uint64_t *n_register_bytes,
                           uint64_t **d_n_kmers, uint64_t *n_slots, uint64_t **d_n_reads, uint64_t *n_nodes);
 

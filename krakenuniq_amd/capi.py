@@ -647,6 +647,17 @@ class Ctx:
              "ku_counts_export")
         return out
 
+    def hll_floors(self):
+        """per-slot lower bounds of the HLL registers the fused kernel filters with (ku_counts_export_floors: a diagnostic the
+        library exports outside the C ABI of the header, bound here and not in SIGNATURES)"""
+        d = CountsDims()
+        _chk(lib().ku_counts_dims_get(self.h, C.byref(d)), "ku_counts_dims_get")
+        out = np.zeros(d.n_slots, dtype=np.uint32)
+        f = lib().ku_counts_export_floors
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, u32p]
+        _chk(f(self.h, _p(out, u32p)), "ku_counts_export_floors")
+        return out
+
     def counts_device_ptrs(self):
         r, k, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
         nb, ns, nn = C.c_uint64(), C.c_uint64(), C.c_uint64()

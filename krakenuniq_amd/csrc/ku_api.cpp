@@ -392,6 +392,7 @@ static void ctx_free_tax(ku_ctx *ctx) {
     *p = nullptr;
   }
   if (ctx->cnt.registers) (void)hipFree(ctx->cnt.registers);
+  if (ctx->cnt.hll_floor) (void)hipFree(ctx->cnt.hll_floor);
   if (ctx->cnt.n_kmers) (void)hipFree(ctx->cnt.n_kmers);
   if (ctx->cnt.n_reads) (void)hipFree(ctx->cnt.n_reads);
   if (ctx->d_exact_set) (void)hipFree(ctx->d_exact_set);
@@ -739,6 +740,7 @@ extern "C" int ku_ctx_set_taxonomy(ku_ctx *ctx, const ku_tax *tax, const uint32_
   // per-taxon state before the stores are finalized: store_finalize remaps the values in place and drops the raw
   // pairs, so nothing that can fail for lack of memory may come after it
   if (hipMalloc((void **)&ctx->cnt.registers, (size_t)slots.size() * KU_HLL_M) != hipSuccess ||
+      hipMalloc((void **)&ctx->cnt.hll_floor, slots.size() * 4) != hipSuccess ||
       hipMalloc((void **)&ctx->cnt.n_kmers, slots.size() * 8) != hipSuccess ||
       hipMalloc((void **)&ctx->cnt.n_reads, nodes.size() * 8) != hipSuccess) {
     (void)hipGetLastError();
@@ -761,6 +763,7 @@ extern "C" int ku_ctx_reset_counts(ku_ctx *ctx) {
   KU_TRY(rle_idle(ctx, "ku_ctx_reset_counts"));
   KU_TRY(ctx_activate(ctx));
   HIP_TRY(hipMemsetAsync(ctx->cnt.registers, 0, (size_t)ctx->tax.n_slots * KU_HLL_M, ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->cnt.hll_floor, 0, (size_t)ctx->tax.n_slots * 4, ctx->stream));  // (floor <= row minimum: KuCountsDev)
   HIP_TRY(hipMemsetAsync(ctx->cnt.n_kmers, 0, (size_t)ctx->tax.n_slots * 8, ctx->stream));
   HIP_TRY(hipMemsetAsync(ctx->cnt.n_reads, 0, (size_t)ctx->tax.n_nodes * 8, ctx->stream));
   if (ctx->d_exact_set) {

@@ -26,6 +26,19 @@ extern "C" int ku_counts_export(ku_ctx *ctx, uint32_t *slot_taxid, uint64_t *n_k
   return KU_OK;
 }
 
+// The fused kernel's HLL floors (KuCountsDev::hll_floor), n_slots values, for the tests (capi.Ctx.hll_floors).  Exported by the
+// library but NOT part of the C ABI of include/krakenuniq_amd.h: a diagnostic of one kernel's internal state.  Behaves like
+// ku_counts_export: KU_ESTATE while batches are in flight.
+extern "C" int ku_counts_export_floors(ku_ctx *ctx, uint32_t *floors) {
+  if (!ctx || !floors) return fail(KU_EINVAL, "ku_counts_export_floors: null argument");
+  if (!ctx->tax_set) return fail(KU_ESTATE, "taxonomy not set");
+  KU_TRY(rle_idle(ctx, "ku_counts_export_floors"));
+  KU_TRY(ctx_activate(ctx));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipMemcpy(floors, ctx->cnt.hll_floor, (size_t)ctx->tax.n_slots * 4, hipMemcpyDeviceToHost));
+  return KU_OK;
+}
+
 // ---------------------------------------------------------------------------- report from the resident state
 namespace {
 struct DevTmp {  // device scratch of one ku_ctx_report call
@@ -317,6 +330,9 @@ extern "C" int ku_ctx_report_cols(ku_ctx *ctx, const ku_tax *tax, const char *co
   return rst;
 }
 
+// Outside writers (the RCCL MAX reduce, merges): the context keeps hll_floor[s] <= min(registers[s][..]) (KuCountsDev) and the fused
+// kernel drops inserts on the strength of it.  Raising registers through these pointers keeps that true; anything that may LOWER
+// one must be followed by ku_ctx_reset_counts, which clears the floors.
 extern "C" int ku_counts_device_ptrs(ku_ctx *ctx, uint8_t **d_registers, uint64_t *n_register_bytes,
                                      uint64_t **d_n_kmers, uint64_t *n_slots, uint64_t **d_n_reads, uint64_t *n_nodes) {
   if (!ctx) return fail(KU_EINVAL, "null context");

@@ -50,6 +50,10 @@ struct KuCountsDev {
   uint8_t *registers;                 // n_slots * 4096, dense HLL p = 12
   unsigned long long *n_kmers;        // n_slots
   unsigned long long *n_reads;        // n_nodes
+  // n_slots: a lower bound of every slot's smallest register, hll_floor[s] <= min(registers[s][0 .. 4095]) at all times.  The fused
+  // kernel keeps it up (ku_short.hip) and drops the inserts it rules out; registers only rise within a run and a floor only rises
+  // (atomicMax), so a stale floor is merely a weaker filter.  Whoever LOWERS a register clears the floors on the same stream.
+  uint32_t *hll_floor;
 };
 
 // Owner routing of the sharded multi-GPU path (ku_mgpu.cpp, ku_route.hip).  A rank scans only its own slice of

@@ -28,6 +28,8 @@
 #ifndef KS_KCT_LOG2
 #define KS_KCT_LOG2 8
 #endif
+#define KS_FLOOR_EVERY 64u  // reads of a wave between two HLL floor scans (env KU_HLL_FLOOR_EVERY; 0 = no floors)
+#define KS_HQ 64            // entries of a wave's queue of deferred HLL inserts (one drain: one entry per lane)
 #define KS_PAD 16   // sentinel elements behind a read's last m-mer (the widest doubling step reads 16 positions ahead)
 #ifdef KU_ABLATION
 #define KS_ABL(bit) ((ablate & (bit)) != 0)
@@ -83,6 +85,13 @@ __device__ __forceinline__ void ks_ct_flush(uint32_t *key, uint32_t *cnt, uint32
   }
   if (lane == 0) *used = 0;
   ks_wave_sync();
+}
+
+// byte-wise unsigned minimum of packed HLL registers (values <= 64 < 128: with bit 7 of every byte of `a` set the subtraction
+// borrows across no byte, and bit 7 of the difference says a >= b)
+__device__ __forceinline__ uint32_t ks_bmin4(uint32_t a, uint32_t b) {
+  const uint32_t m = ((((a | 0x80808080u) - b) & 0x80808080u) >> 7) * 0xFFu;
+  return (b & m) | (a & ~m);
 }
 
 // n_reads counter table of a wave: keys are taxonomy nodes, or KS_RCT_SLOT | slot for the reads that met a single
@@ -210,6 +219,34 @@ __device__ __forceinline__ uint32_t ks_tab_resolve(uint32_t *t_key, uint32_t *t_
 __device__ __forceinline__ uint32_t ks_gload(const uint32_t *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// HLL floors: the wave raises the floor of slot `rs` to the smallest register of the slot's 4 KB row (the kernel's comment).  A call,
+// not inline: it runs once in many reads, and inline it costs the read loop vector registers it does not have.
+__device__ __noinline__ void ks_floor_scan(const uint8_t *registers, uint32_t *hll_floor, uint32_t rs, uint32_t lane) {
+  const uint4 *row = reinterpret_cast<const uint4 *>(registers + (size_t)rs * KU_HLL_M) + 4 * lane;  // 64 B per lane
+  const uint32_t cur = ks_gload(&hll_floor[rs]);
+  uint32_t lo = 0x7f7f7f7fu;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint4 x = row[q];
+    lo = ks_bmin4(lo, ks_bmin4(ks_bmin4(x.x, x.y), ks_bmin4(x.z, x.w)));
+  }
+  lo = min(min(lo & 0xffu, (lo >> 8) & 0xffu), min((lo >> 16) & 0xffu, lo >> 24));
+  lo = ku_wave_min_u32(lo);
+  if (lane == 0 && lo > cur) atomicMax(&hll_floor[rs], lo);
+}
+
+// The wave's queue of deferred HLL inserts (the kernel's comment): every lane takes one entry -- {slot, register index | rank << 12}
+// -- and the register bytes of all of them are requested together.  A call for the same reason as ks_floor_scan.
+__device__ __noinline__ void ks_hq_drain(const uint2 *q, uint32_t fill, uint8_t *registers, uint32_t lane) {
+  ks_wave_sync();
+  if (lane < fill) {
+    const uint2 e = q[lane];
+    uint8_t *r = registers + (size_t)e.x * KU_HLL_M + (e.y & (KU_HLL_M - 1u));
+    ku_hll_raise(r, (uint32_t)*r, e.y >> KU_HLL_P);
+  }
+  ks_wave_sync();
+}
+
 __device__ __noinline__ void ks_spill_add(uint32_t *g_key, uint32_t *g_cnt, uint32_t mask, uint32_t slot, uint32_t count) {
   uint32_t h = (slot * 2654435761u) & mask;
   for (;;) {
@@ -351,8 +388,8 @@ template <int ITEMS, bool DO_COUNTS, int KK, int MM, bool WIN, int OUT, bool ROU
 __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_short_kernel(
     KuDbDev db, KuTaxDev tax, KuCountsDev cnt, const uint8_t *__restrict__ seqs, uint64_t n_bytes,
     const uint64_t *__restrict__ seq_off, const uint32_t *__restrict__ seq_len, uint64_t n_reads,
-    uint32_t *__restrict__ calls, uint32_t *__restrict__ taxa, uint32_t ablate, uint32_t *__restrict__ spill,
-    uint32_t spill_cap, KuRunsOut ro, KuSparseFast sf, KuRouteIn rin) {
+    uint32_t *__restrict__ calls, uint32_t *__restrict__ taxa, uint32_t ablate, uint32_t floor_every,
+    uint32_t *__restrict__ spill, uint32_t spill_cap, KuRunsOut ro, KuSparseFast sf, KuRouteIn rin) {
   // KS_ABL(bit): measurement knob, compiled in only with -DKU_ABLATION (then env KU_ABLATE selects the bits; the
   // production build has no trace of it -- the flag checks cost scalar registers and branches in the read loop):
   // 1 skip probe, 2 skip HLL, 4 skip n_kmers, 8 skip taxa store,
@@ -369,6 +406,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
   __shared__ uint16_t s_tlist[KS_WAVES][WIN ? (int)TCAP : G::MAXN];
   __shared__ uint32_t s_kk[KS_WAVES][1 << G::KCT_LOG2], s_kc[KS_WAVES][1 << G::KCT_LOG2];
   __shared__ uint32_t s_rk[KS_WAVES][1 << G::RCT_LOG2], s_rc[KS_WAVES][1 << G::RCT_LOG2];
+  __shared__ uint2 s_hq[KS_WAVES][DO_COUNTS && !ROUTE ? KS_HQ : 1];  // deferred HLL inserts
   __shared__ uint32_t s_misc[KS_WAVES][4];      // [0] n_kmers table fill, [1] n_reads table fill, [2] list length, [3] WIN: distinct taxa in the table
 
   const uint32_t lane = threadIdx.x & 63u;
@@ -440,6 +478,25 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     ch_end = b + want;
   };
   uint32_t sp_fresh = 0;  // OUT == 2: entries this wave added to G
+  // HLL floors (KuCountsDev::hll_floor; floor_every = 0: none of it).  A k-mer whose rank does not exceed the floor of its slot
+  // cannot raise its register and is dropped before the register's address is formed: once a slot has seen a few hundred
+  // thousand k-mers that is nearly all of them, and the register rows are the one part of the kernel's traffic the caches do not
+  // hold.  The kernel keeps the floors up itself: every floor_every-th read (window) a wave scans the 4 KB row of a slot the read
+  // just booked, in turn its first hit's slot and slot 0 (the misses'), and raises that floor to the row's minimum.  The scan may
+  // see stale, i.e. smaller, registers and a loaded floor may be stale, i.e. smaller: both only weaken the filter.
+  // The scan (ks_floor_scan) waits for the top of the next read, or the end of the kernel.  The waves start at different counts,
+  // so that launches of a few reads per wave (the `classify` executable's) scan as well.
+  uint32_t fl_reads =  // reads since the wave's last scan | bit 31: whose turn the next one is
+      floor_every ? (((uint32_t)blockIdx.x * KS_WAVES + wv) * 40503u >> 8) % floor_every : 0u;
+  uint32_t fl_scan = 0;  // slot + 1 of the scan that is due (0 = none); both wave-uniform
+  // What the floors let through is a handful of k-mers per read, and nothing in the kernel reads a register but the scan, which
+  // may see them late: they are not waited for.  The wave packs them into a queue of its own in LDS (a ballot per item, the
+  // lanes' places by mbcnt) and drains it -- every lane one entry, all register bytes requested together, ku_hll_raise as ever
+  // -- when the next read's do not fit, and at the end of the kernel: one round trip to the registers in ten or twenty reads
+  // instead of one per read.  A read with more than half a queue of them (cold floors, a rare taxon, floor_every = 0) takes
+  // the direct way: request all, raise.
+  uint32_t hq_fill = 0;  // entries in the queue (wave-uniform)
+  uint2 *hq = s_hq[wv];
 #ifdef KS_PREFETCH
   // software pipeline over the wave's reads: the text of the NEXT read is requested before the current one is worked
   // on (its latency hides behind a whole read's worth of work), its length / offset one read earlier still
@@ -506,6 +563,10 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     const uint64_t off = roff + win0;
     const uint32_t n = len >= k ? len - k + 1 : 0;
     if (DO_COUNTS) {
+      if (!ROUTE && fl_scan) {
+        ks_floor_scan(cnt.registers, cnt.hll_floor, fl_scan - 1u, lane);
+        fl_scan = 0;
+      }
       if (!ROUTE && misc[0] > (1u << G::KCT_LOG2) / 2) ks_ct_flush<G::KCT_LOG2>(s_kk[wv], s_kc[wv], &misc[0], cnt.n_kmers, lane);
       if (!WIN || win0 == 0)
         if (misc[1] > (1u << G::RCT_LOG2) / 2) ks_rct_flush<G::RCT_LOG2>(s_rk[wv], s_rc[wv], &misc[1], tax, cnt.n_reads, lane);
@@ -831,6 +892,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     // ---- resolve_tree (krakenutil.cpp:149-200) from registers
     bool uni = false;        // at most one distinct hit taxon in the read / window (the common case)
     uint32_t uni_slot = 0;   // that taxon's slot (0 = no hit at all)
+    uint32_t hit_first = 0;  // slot of the first k-mer with a hit (0 = none): whose HLL floor a scan refreshes
     if (!KS_ABL(32u)) {
       uint32_t mine = 0;
 #pragma unroll
@@ -843,6 +905,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
       for (int j = 0; j < ITEMS; ++j) diff |= (v[j] != 0 && v[j] != first);
       uni = !__any(diff);
       uni_slot = uni ? first : 0u;
+      hit_first = first;
       if (!WIN) {
         // at most one distinct hit taxon: the call is that taxon (its taxid comes from the slot table below, the read
         // counter is keyed by the slot); else hit_counts in the wave's LDS table
@@ -898,18 +961,56 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
 
     // the taxid of the single taxon is requested here: its round trip runs under the HLL loads below
     const uint32_t uni_code = uni && uni_slot ? tax.slot_taxid[uni_slot] : 0u;
+    // so are the two HLL floors such a read needs, the misses' and the taxon's (past this CU's L1, which another CU's raise of
+    // a floor never reaches)
+    const bool fl_on = DO_COUNTS && !ROUTE && floor_every != 0 && n > 0;
+    uint32_t fl_miss = 0, fl_hit = 0;
+    if (fl_on && uni) {
+      fl_miss = ks_gload(&cnt.hll_floor[0]);
+      fl_hit = ks_gload(&cnt.hll_floor[uni_slot]);
+    }
 
     // ---- ReadCounts::add_kmer for every unambiguous k-mer, misses included (classify.cpp:939): HLL register per
     // k-mer; n_kmers per read when the read met one taxon at most (two counter updates instead of one per lane)
     uint32_t n_hit = 0, n_miss = 0;
     if (DO_COUNTS && !ROUTE && n > 0) {
       uint8_t *reg[ITEMS];
-      uint32_t rank[ITEMS], seen[ITEMS];
+      uint32_t rank[ITEMS], seen[ITEMS], fl[ITEMS];
+      if (fl_on && !uni) {  // several taxa: each lane fetches the floors of its own slots
 #pragma unroll
-      for (int j = 0; j < ITEMS; ++j) {  // every register byte is requested before the first one is looked at
+        for (int j = 0; j < ITEMS; ++j) fl[j] = ks_gload(&cnt.hll_floor[v[j]]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) fl[j] = v[j] ? fl_hit : fl_miss;
+      }
+      bool go[ITEMS];
+      unsigned long long gob[ITEMS];
+      uint32_t n_go = 0;
+#pragma unroll
+      for (int j = 0; j < ITEMS; ++j) {
         const bool okc = j * 64 + lane < n && !amb_k[j];
         reg[j] = ku_hll_locate(cnt.registers, okc ? v[j] : 0u, hh[j], rank[j]);
-        seen[j] = (okc && !KS_ABL(2u)) ? (uint32_t)*reg[j] : 0xFFu;
+        go[j] = okc && rank[j] > fl[j] && !KS_ABL(2u);
+        gob[j] = __ballot(go[j]);
+        n_go += (uint32_t)__popcll(gob[j]);
+      }
+      const bool direct = !fl_on || n_go > KS_HQ / 2;  // wave-uniform
+      if (direct) {
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j)  // every register byte is requested before the first one is looked at
+          seen[j] = go[j] ? (uint32_t)*reg[j] : 0xFFu;  // (0xFF: nothing to raise)
+      } else {
+        if (hq_fill + n_go > KS_HQ) {
+          ks_hq_drain(hq, hq_fill, cnt.registers, lane);
+          hq_fill = 0;
+        }
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+          const uint32_t at = hq_fill + __builtin_amdgcn_mbcnt_hi((uint32_t)(gob[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)gob[j], 0u));
+          if (go[j]) hq[at] = make_uint2(v[j], (uint32_t)(hh[j] >> (64 - KU_HLL_P)) | (rank[j] << KU_HLL_P));
+          hq_fill += (uint32_t)__popcll(gob[j]);
+          seen[j] = 0xFFu;
+        }
       }
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) {
@@ -925,6 +1026,10 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
       if (uni && lane == 0 && !KS_ABL(4u)) {
         if (n_hit) ku_ct_add<G::KCT_LOG2>(s_kk[wv], s_kc[wv], &misc[0], uni_slot, n_hit, cnt.n_kmers);
         if (n_miss) ku_ct_add<G::KCT_LOG2>(s_kk[wv], s_kc[wv], &misc[0], 0u, n_miss, cnt.n_kmers);
+      }
+      if (fl_on && ((++fl_reads) & 0x7fffffffu) >= floor_every) {  // a scan is due: the turn changes, the count starts again
+        fl_reads = ~fl_reads & 0x80000000u;
+        fl_scan = ((fl_reads >> 31) ? hit_first : 0u) + 1u;
       }
     }
 
@@ -1097,6 +1202,8 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     // the counters every wave holds -- misses (slot 0), reads without a hit (node 0) -- leave the block as ONE add each
     __shared__ uint32_t s_hot[KS_WAVES][2];
     if (lane < 2) s_hot[wv][lane] = 0;
+    if (!ROUTE && hq_fill) ks_hq_drain(hq, hq_fill, cnt.registers, lane);
+    if (!ROUTE && fl_scan) ks_floor_scan(cnt.registers, cnt.hll_floor, fl_scan - 1u, lane);
     if (!ROUTE) ks_ct_flush<G::KCT_LOG2>(s_kk[wv], s_kc[wv], &misc[0], cnt.n_kmers, lane, &s_hot[wv][0]);
     ks_rct_flush<G::RCT_LOG2>(s_rk[wv], s_rc[wv], &misc[1], tax, cnt.n_reads, lane, &s_hot[wv][1]);
     __syncthreads();  // (every wave of the block reaches the end of the kernel: the only block barrier in it)
@@ -1162,6 +1269,9 @@ int ku_launch_classify_short(const KuDbDev &db, const KuTaxDev &tax, const KuCou
   if (d_hits && hipMemsetAsync(d_hits, 0, n_reads * 4, stream) != hipSuccess) return KU_EHIP;  // "Q:n" is quick mode only
   const char *ab = getenv("KU_ABLATE");
   const uint32_t ablate = ab ? (uint32_t)atoi(ab) : 0u;
+  // reads of a wave between two refreshes of an HLL floor (the kernel's comment); 0: no floors, every register is looked at
+  const char *fe = getenv("KU_HLL_FLOOR_EVERY");
+  const uint32_t floor_every = fe ? (uint32_t)(atoi(fe) > 0 ? atoi(fe) : 0) : KS_FLOOR_EVERY;
   const bool windowed = max_kmers > ks_one_pass_max();
   const int items = max_kmers <= 128 || windowed ? 2 : 3;
   const dim3 grid(ks_grid(n_reads, items, n_cu)), block(64 * KS_WAVES);
@@ -1176,7 +1286,8 @@ int ku_launch_classify_short(const KuDbDev &db, const KuTaxDev &tax, const KuCou
   const int out = sparse ? 2 : (runs_out ? 1 : 0);
 #define KS_LAUNCH(I, C, K, M, W, O)                                                                                          \
   hipLaunchKernelGGL((ku_classify_short_kernel<I, C, K, M, W, O>), grid, block, 0, stream, db, tax, cnt, d_seqs, n_bytes,    \
-                     d_seq_off, d_seq_len, n_reads, d_calls, d_taxa, ablate, (uint32_t *)d_workspace, spill_cap, ro, sf, KuRouteIn{})
+                     d_seq_off, d_seq_len, n_reads, d_calls, d_taxa, ablate, floor_every, (uint32_t *)d_workspace, spill_cap, ro, sf,   \
+                     KuRouteIn{})
   // specialised geometries (accounting runs only): k = 31 with nt = 13 (MiniKraken-size databases) or 15 (standard)
   const int geo = !counts || db.k != 31 ? 0 : (db.nt == 13 ? 13 : (db.nt == 15 ? 15 : 0));
 #define KS_GEO(I, W, O)                                      \
@@ -1224,7 +1335,7 @@ int ku_launch_route_resolve(const KuDbDev &db, const KuTaxDev &tax, const KuCoun
   const KuRouteIn rin{d_kb, d_ret};
 #define KS_RLAUNCH(C, W, O)                                                                                                     \
   hipLaunchKernelGGL((ku_classify_short_kernel<2, C, 0, 0, W, O, true>), grid, block, 0, stream, db, tax, cnt, (const uint8_t *)nullptr, \
-                     (uint64_t)0, d_seq_off, d_seq_len, n_reads, d_calls, d_taxa, 0u, (uint32_t *)d_workspace, spill_cap, ro,    \
+                     (uint64_t)0, d_seq_off, d_seq_len, n_reads, d_calls, d_taxa, 0u, 0u, (uint32_t *)d_workspace, spill_cap, ro, \
                      KuSparseFast{}, rin)
 #define KS_RSEL(W, O)                  \
   do {                                 \
