@@ -38,7 +38,6 @@ void Run::device_stage_chunked() {
   for (size_t r = 0; r < n_ranks_x; ++r) {
     cs[r].c = r == 0 ? ctx : helpers[r - 1];
     cs[r].list = &rank_chunks[r];
-    cs[r].off = getenv("KU_NO_PREFETCH") != nullptr;
   }
   auto start_prefetch = [&](ChunkStream &st, size_t c) {
     if (st.off) return;
@@ -146,8 +145,10 @@ void Run::device_stage_resident() {
 // this thread waits for one event per batch (one step per batch cost ~1 ms of fixed time each, four times the kernels'; VERDICT
 // r04 weak #3).  Groups (KU_DEVICES) and UID mapping (whose calls are replaced batch by batch) go one batch at a time.
 const bool two_step = !mg && !map_uids && !getenv("KU_RLE_ONE_STEP");
-// (a batch's way through the device is ~1 ms of dependent steps around a 0.2 ms kernel: three in flight hide it)
-const size_t depth = getenv("KU_RLE_DEPTH") ? (size_t)std::min(std::max(atoi(getenv("KU_RLE_DEPTH")), 1), KU_RLE_MAX_IN_FLIGHT) : 3;
+// (a batch's way through the device is ~1 ms of dependent steps around a 0.2 ms kernel: three in flight hide it;
+// profiles/r05_e2e_sweep.log, the two-step call at 1..4 in flight)
+constexpr size_t depth = 3;
+static_assert(depth <= KU_RLE_MAX_IN_FLIGHT, "more batches in flight than the two-step call admits");
 std::deque<Batch *> flying;
 uint64_t runs_seen_max = 0;  // extent of the largest run array so far: the next batches' buffers take it in one go
 auto finish_oldest = [&] {

@@ -77,15 +77,13 @@ bool Run::parse_file_in_regions(const char *path) {
 #ifdef MADV_POPULATE_READ
       if (direct) {  // the region's pages into this process's page table with one call instead of one fault per 4 KiB (eight
                      // threads faulting in one address space queue on its locks: a third of the team's time); failure is harmless
-        static const bool populate = !(getenv("KU_NO_POPULATE") && atoi(getenv("KU_NO_POPULATE")));
         // (2 MiB per call: the call holds the address space's lock shared for as long as it runs, and a thread that wants it
         // exclusively -- any mmap / munmap, e.g. under malloc or in the GPU runtime -- waits for every holder while it keeps all
         // new ones out, page faults included.  With a region per call, twelve members held it ~10 ms each at the start of a
         // file and the whole process stood still for ~20 ms: the pipeline trace in profiles/r05_e2e_sweep.log)
-        static const size_t step = (size_t)std::max(1, getenv("KU_POPULATE_MB") ? atoi(getenv("KU_POPULATE_MB")) : 2) << 20;
+        constexpr size_t step = (size_t)2 << 20;
         const size_t pg = 4096, a0 = lo & ~(pg - 1);
-        if (populate)
-          for (size_t a = a0; a < hi; a += step) (void)madvise((void *)(data + a), std::min(step, hi - a), MADV_POPULATE_READ);
+        for (size_t a = a0; a < hi; a += step) (void)madvise((void *)(data + a), std::min(step, hi - a), MADV_POPULATE_READ);
       }
 #endif
       // (the records that START in the region, each read to its end wherever that lies: ku_seqio::parse_region)
@@ -98,7 +96,8 @@ bool Run::parse_file_in_regions(const char *path) {
   std::vector<std::thread> team;
   // (a .gz / .bz2 file: the inflating team is the slowest stage and wants the cores -- six parsers keep up with it; measured
   // on the 16-CPU quota of the GPU box, 10 M reads from one gzip stream: 0.368-0.372 s with 6, 0.381-0.412 with 12)
-  const int members = direct ? parse_team : std::min(parse_team, getenv("KU_PARSE_TEAM_GZ") ? std::max(1, atoi(getenv("KU_PARSE_TEAM_GZ"))) : 6);
+  constexpr int parse_team_gz = 6;
+  const int members = direct ? parse_team : std::min(parse_team, parse_team_gz);
   for (int t = 0; t < members; ++t) team.emplace_back(member);
   // The batches go on in file order.  A region counts iff the parse of the region before it stopped exactly at its start
   // (ku_seqio::RegionChain: a region cut inside a record -- damaged FASTQ -- is parsed again from there, by this thread); the

@@ -118,7 +118,8 @@ int Run::run(int argc_, char **argv_) {
   if (!(getenv("KU_MALLOPT") && atoi(getenv("KU_MALLOPT")) == 0)) {
     mallopt(M_MMAP_THRESHOLD, 1 << 30);
     mallopt(M_TRIM_THRESHOLD, 1 << 30);
-    mallopt(M_TOP_PAD, getenv("KU_TOP_PAD_MB") ? atoi(getenv("KU_TOP_PAD_MB")) << 20 : 16 << 20);  // (a thread's heap grows by mprotect -- exclusive, too: in few large steps)
+    constexpr int top_pad_bytes = 16 << 20;
+    mallopt(M_TOP_PAD, top_pad_bytes);  // (a thread's heap grows by mprotect -- exclusive, too: in few large steps)
   }
   int opt;
   while ((opt = getopt(argc, argv, "d:i:t:u:n:m:o:qcC:U:Ma:r:sI:p:x:P")) != -1) {

@@ -296,15 +296,11 @@ int rle_idle(const ku_ctx *ctx, const char *who) {
 static int rle_job_enqueue(ku_ctx *ctx, RleJob &j, const char *seqs, uint64_t n_bytes, const uint64_t *seq_off, const uint32_t *seq_len,
                            uint64_t n_reads, const ku_opts &o, uint32_t max_n, bool monotonic, uint32_t *calls, uint32_t *hits,
                            uint64_t *run_off, uint32_t *run_cnt, ku_run *h_runs, uint64_t h_runs_cap) {
-  // the batch's kernels: consecutive batches take the two kernel streams in turn (KU_RLE_KERNEL_STREAMS=1: the context's one stream)
-  static const bool one_kernel_stream = getenv("KU_RLE_KERNEL_STREAMS") && atoi(getenv("KU_RLE_KERNEL_STREAMS")) == 1;
-  hipStream_t s = ctx->stream;
-  if (!one_kernel_stream) {
-    hipStream_t &ks = ctx->k_streams[(&j - &ctx->rle[0]) & 1];
-    if (!ks) HIP_TRY(hipStreamCreateWithFlags(&ks, hipStreamNonBlocking));
-    if (!ctx->main_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->main_ev, hipEventDisableTiming));
-    s = ks;
-  }
+  // the batch's kernels: consecutive batches take the two kernel streams in turn (never the context's own stream, ku_ctx.h)
+  hipStream_t &ks = ctx->k_streams[(&j - &ctx->rle[0]) & 1];
+  if (!ks) HIP_TRY(hipStreamCreateWithFlags(&ks, hipStreamNonBlocking));
+  if (!ctx->main_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->main_ev, hipEventDisableTiming));
+  const hipStream_t s = ks;
   const double t_in = g_rle_times ? rle_now() : 0.0;
   const bool counts = !(o.flags & KU_F_NO_COUNTS);
   const bool sparse = ctx->sp.on && counts;
@@ -314,7 +310,7 @@ static int rle_job_enqueue(ku_ctx *ctx, RleJob &j, const char *seqs, uint64_t n_
   uint64_t n_seg = 1;
   // (16 MiB per segment since round 5 -- was 8: with several batches in flight the overlap of upload and kernels comes from the
   // OTHER batches, and a launch of 120 k reads costs 3.0 us per thousand reads where two of 60 k cost 3.8, ku_short.hip)
-  static const uint64_t seg_bytes = (uint64_t)std::max(1, getenv("KU_RLE_SEG_MB") ? atoi(getenv("KU_RLE_SEG_MB")) : 16) << 20;
+  constexpr uint64_t seg_bytes = 16ull << 20;
   if (monotonic && !getenv("KU_NO_H2D_OVERLAP")) n_seg = std::min<uint64_t>(8, std::max<uint64_t>(1, n_bytes / seg_bytes));
   std::vector<uint64_t> seg(n_seg + 1, 0);
   for (uint64_t g = 1; g < n_seg; ++g) {
@@ -401,10 +397,9 @@ static int rle_job_enqueue(ku_ctx *ctx, RleJob &j, const char *seqs, uint64_t n_
   unsigned long long *h_tot = (unsigned long long *)j.pin.p;
   h_flag = (uint8_t *)j.pin.p + 64;
   if (g_rle_times) g_rle_t[5] += rle_now() - t_in;
-  if (s != ctx->stream) {  // whatever was queued on the context's own stream before this batch comes first
-    HIP_TRY(hipEventRecord(ctx->main_ev, ctx->stream));
-    HIP_TRY(hipStreamWaitEvent(s, ctx->main_ev, 0));
-  }
+  // whatever was queued on the context's own stream before this batch comes first
+  HIP_TRY(hipEventRecord(ctx->main_ev, ctx->stream));
+  HIP_TRY(hipStreamWaitEvent(s, ctx->main_ev, 0));
   unsigned long long *d_counter = j.d_counter;
   // (emulation) the per-(unit, slot) insert counts and the unit flags start at zero: one launch
   if (sparse) {
@@ -462,7 +457,7 @@ static int rle_job_enqueue(ku_ctx *ctx, RleJob &j, const char *seqs, uint64_t n_
     // The open unit's insert counts (sp.tail_row) travel from batch to batch through this small step behind the kernels: it
     // reads what the batch before wrote behind ITS kernels on the other stream, and what it writes must not land before that
     // batch has read -- so the step (not the kernels) waits for the whole of the batch before, in enqueue order.
-    if (ctx->prev_kernels_done && s != ctx->stream) HIP_TRY(hipStreamWaitEvent(s, ctx->prev_kernels_done, 0));
+    if (ctx->prev_kernels_done) HIP_TRY(hipStreamWaitEvent(s, ctx->prev_kernels_done, 0));
     // unit 0 continues the open unit: the inserts that unit had before this batch join its row
     if (j.cont_tail && j.n_units)
       KU_TRY(ku_launch_add_u32((uint32_t *)j.u_cnt.p, (const uint32_t *)sp.tail_row.p, ctx->tax.n_slots, s));
@@ -475,13 +470,10 @@ static int rle_job_enqueue(ku_ctx *ctx, RleJob &j, const char *seqs, uint64_t n_
   }
   if (g_rle_times && clock_started) HIP_TRY(hipEventRecord(j.t_k1, s));
   // ---- the copies back run on a stream of their own, behind this batch's kernels -- not in front of the next batch's
-  static const bool own_d2h_stream = !(getenv("KU_RLE_D2H_STREAM") && atoi(getenv("KU_RLE_D2H_STREAM")) == 0);
-  hipStream_t ds = own_d2h_stream ? ctx->d2h_stream : s;
+  const hipStream_t ds = ctx->d2h_stream;
   HIP_TRY(hipEventRecord(j.kernels_done, s));
   ctx->prev_kernels_done = j.kernels_done;  // (the jobs' events live as long as the context)
-  if (own_d2h_stream) {
-    HIP_TRY(hipStreamWaitEvent(ds, j.kernels_done, 0));
-  }
+  HIP_TRY(hipStreamWaitEvent(ds, j.kernels_done, 0));
   HIP_TRY(hipMemcpyAsync(calls, j.calls.p, n_reads * 4, hipMemcpyDeviceToHost, ds));
   HIP_TRY(hipMemcpyAsync(run_off, j.roff.p, n_reads * 8, hipMemcpyDeviceToHost, ds));
   HIP_TRY(hipMemcpyAsync(run_cnt, j.rcnt.p, n_reads * 4, hipMemcpyDeviceToHost, ds));

@@ -682,7 +682,7 @@ extern "C" int ku_mgpu_create(const int *devices, uint32_t n_local, uint32_t fir
   std::set<int> distinct(devices, devices + n_local);
   // KU_MGPU_FORCE_RCCL=1 takes the RCCL calls even for a world of one rank (a way to exercise them on a 1-GPU box)
   m->use_rccl = (world > 1 || getenv("KU_MGPU_FORCE_RCCL")) &&
-                (!all_here || (distinct.size() == n_local && !(flags & KU_MGPU_NO_RCCL) && !getenv("KU_MGPU_NO_RCCL")));
+                (!all_here || (distinct.size() == n_local && !(flags & KU_MGPU_NO_RCCL)));
   if (n_local > 1) {
     if (pthread_barrier_init(&m->sh.bar, nullptr, n_local) != 0) { delete m; return mfail(KU_ENOMEM, "pthread_barrier_init"); }
     m->sh.bar_init = true;

@@ -503,7 +503,7 @@ struct Reader {
         return;
       }
     }
-    if (prefetch && g && S_ISREG(st.st_mode) && !getenv("KU_NO_BGZF") && open_bgzf(path, (size_t)st.st_size)) {
+    if (prefetch && g && S_ISREG(st.st_mode) && open_bgzf(path, (size_t)st.st_size)) {
       more();
       fastq = len > 0 && buf[0] == '@';
       return;
@@ -881,7 +881,7 @@ inline RegionParse parse_region(const char *text, size_t text_n, GrowingText *gt
                                 bool keep_records) {
   RegionParse res;
   size_t at = lo;
-  if (fastq && !getenv("KU_SEQIO_GENERAL")) {  // whole four-line records inside [lo, hi): the fast path
+  if (fastq) {  // whole four-line records inside [lo, hi): the fast path
     at += parse_fastq_fast(text + lo, hi - lo, bt, keep_records);
     if (at == hi) { res.end = hi; return res; }
   }
@@ -1088,7 +1088,7 @@ struct GzTextStream {
       });
       return true;
     }
-    if (!getenv("KU_NO_BGZF") && plan_bgzf()) {
+    if (plan_bgzf()) {
       int n = std::max(1, std::min(hw, 8));
       if (const char *e = getenv("KU_BGZF_TEAM")) n = std::max(1, std::min(atoi(e), 64));
       task_done.assign(tasks.size(), 0);

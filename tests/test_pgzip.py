@@ -66,8 +66,8 @@ def zlib_accepts(blob):
     return True
 
 
-def inflate(path, team, span_kb=None):
-    env = dict(os.environ)
+def inflate(path, team, span_kb=None, **more_env):
+    env = dict(os.environ, **more_env)
     if span_kb:
         env["KU_PGZIP_SPAN_KB"] = str(span_kb)
     return subprocess.run([DUMP, "-z", str(team), str(path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
@@ -112,6 +112,10 @@ def test_team_inflate_equals_zlib(shape, tmp_path):
             r = inflate(p, team, span_kb)
             assert r.returncode == 0, (shape, team, span_kb, r.stderr.decode()[-300:])
             assert r.stdout == want, (shape, team, span_kb, len(r.stdout), len(want))
+    if shape == "many_members":  # zlib's crc32, which a CPU without pclmul / sse4.1 takes by itself: every member's trailer holds
+        r = inflate(p, 4, KU_PGZIP_ZLIB_CRC="1")
+        assert r.returncode == 0, (shape, "zlib crc", r.stderr.decode()[-300:])
+        assert r.stdout == want, (shape, "zlib crc", len(r.stdout), len(want))
 
 
 def test_highly_compressible_spans_hand_over_early(tmp_path):
@@ -155,6 +159,8 @@ def test_damaged_files_are_refused(damage, tmp_path):
         for span_kb in (None, 64):
             r = inflate(p, team, span_kb)
             assert r.returncode != 0, (damage, team, span_kb)
+    if damage == "bad_crc":  # ... and by zlib's crc32 (a CPU without pclmul / sse4.1)
+        assert inflate(p, 4, KU_PGZIP_ZLIB_CRC="1").returncode != 0, (damage, "zlib crc")
 
 
 def test_reader_takes_plain_gz_through_the_team(tmp_path):
