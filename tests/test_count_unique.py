@@ -16,6 +16,7 @@ import pytest
 
 from krakenuniq_amd import capi, synth
 from oracle import ku_oracle as ko
+from built_kmers import unmix
 from test_kmer_db import (_VALID, _kmer_db, _ref, _same_file, _trial_records, _want, model_kmers, passes_that_fit,
                           trial, valid_windows)  # noqa: F401  (trial: the module's fixture, with its reference files)
 
@@ -282,17 +283,6 @@ def test_cuts_and_packing(k):
     assert n0 == n_observed and np.array_equal(regs0, regs)
 
 
-def _unmix(h):
-    """the value whose hash (murmurhash3_finalizer of value + 1) is h: both multipliers are odd, x ^= x >> 33 undoes itself"""
-    x = h
-    x ^= x >> 33
-    x = x * pow(0xc4ceb9fe1a85ec53, -1, 1 << 64) & M64
-    x ^= x >> 33
-    x = x * pow(0xff51afd7ed558ccd, -1, 1 << 64) & M64
-    x ^= x >> 33
-    return (x - 1) & M64
-
-
 def _built_hashes(p):
     m = 1 << p
     return [0, (m - 1) << (64 - p), ((5 % m) << (64 - p)) | 1, ((3 % m) << (64 - p)) | (1 << (63 - p))]
@@ -301,14 +291,14 @@ def _built_hashes(p):
 def test_unmix_inverts_the_hash():
     for p in PS:
         for h in _built_hashes(p):
-            assert ko.lib().ko_hash(_unmix(h)) == h
+            assert ko.lib().ko_hash(unmix(h)) == h
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("p", PS)
 def test_built_hashes_through_add_values(p):
     m = 1 << p
-    values = np.array([_unmix(h) for h in _built_hashes(p)], dtype=np.uint64)
+    values = np.array([unmix(h) for h in _built_hashes(p)], dtype=np.uint64)
     want = oracle_registers(values, p)
     # no bit behind the index: the saturated rank, at index 0 and at the last one; the lowest bit alone: one less; the first: 1
     assert {i: int(want[i]) for i in np.flatnonzero(want)} == {0: 64 - p + 1, m - 1: 64 - p + 1, 5 % m: 64 - p, 3 % m: 1}
