@@ -49,6 +49,28 @@ template <int ITEMS> struct KsGeom {
   static constexpr int RCT_LOG2 = 6;                           // n_reads counter table (per wave)
 };
 
+// Everything a wave keeps in LDS, as ONE block: every address is the wave's base (one scalar) plus a compile-time offset that
+// rides in the DS instruction's immediate field.  (Twelve arrays of their own had twelve bases, which the register allocator
+// parked in VGPR lanes and read back inside the read loop.)  An instance carries only what it uses: SCAN -- stages 1-4 run
+// here (not ROUTE); HQ -- the queue of deferred HLL inserts (accounting, not ROUTE).  The 8-byte queue entries come first and
+// are the only member that asks for more than dword alignment.
+template <int ITEMS, bool WIN, bool SCAN, bool HQ> struct KsWaveLds {
+  using G = KsGeom<ITEMS>;
+  static constexpr int TCAP = 1 << G::TCAP_LOG2;
+  std::conditional_t<HQ, uint2, uint32_t> hq[HQ ? KS_HQ : 0];  // deferred HLL inserts
+  uint32_t codes[SCAN ? G::NCODES : 0];
+  uint32_t amb[SCAN ? G::NAMB : 0];             // (stage 1 writes it in 16-bit halves)
+  uint32_t mm[SCAN ? G::NMM : 0];
+  uint32_t tkey[TCAP];                          // resolve table: slot + 1
+  uint32_t tcnt[TCAP];                          // hit count (low 16) | root-path score (high 16)
+  uint32_t kk[SCAN ? 1 << G::KCT_LOG2 : 0], kc[SCAN ? 1 << G::KCT_LOG2 : 0];
+  uint32_t rk[1 << G::RCT_LOG2], rc[1 << G::RCT_LOG2];
+  // [0] n_kmers table fill, [1] n_reads table fill, [2] list length, [3] WIN: distinct taxa in the table; behind the last read
+  // [2] and [3] carry the wave's two hot counters to the block's sum (the end of the kernel)
+  uint32_t misc[4];
+  uint16_t tlist[WIN ? TCAP : G::MAXN];
+};
+
 // Four dwords of a table line at dword alignment: ONE 16-byte load that is either an entry with the dword behind it (entry i
 // lies at dword 4 + 3 i of its line; the fourth dword of entry 7 is the first SEEN word, still inside the line) or, aimed at
 // dword 0 of a line, that line's header.
@@ -57,6 +79,10 @@ struct __attribute__((packed, aligned(4))) KsQuad {
 };
 __device__ __forceinline__ uint64_t ks_quad_key(const KsQuad &q) { return ((uint64_t)q.y << 32) | q.x; }  // as an entry: key_lo, key_hi, slot
 __device__ __forceinline__ uint4 ks_quad_header(const KsQuad &q) { return make_uint4(q.x, q.y, q.z, q.w); }
+
+// a < b for wave-uniform 64-bit counts and offsets (both below 2^63): the sign of a scalar subtract.  (The 64-bit unsigned compares
+// exist as vector instructions only: a wave-uniform one costs two moves into vector registers and a compare at a quarter of the rate.)
+__device__ __forceinline__ bool ks_less64(uint64_t a, uint64_t b) { return (int64_t)(a - b) < 0; }
 
 // order the wave's own LDS traffic (hardware executes a wave's DS ops in order; this stops the compiler)
 __device__ __forceinline__ void ks_wave_sync() {
@@ -398,51 +424,31 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
   // straggler pass (a lookup that the first entry compare leaves open stays a miss: wrong for spilled k-mers).  0 in production.
   using G = KsGeom<ITEMS>;
   constexpr uint32_t TCAP = 1u << G::TCAP_LOG2;
-  __shared__ uint32_t s_codes[KS_WAVES][G::NCODES];
-  __shared__ uint32_t s_amb[KS_WAVES][G::NAMB];
-  __shared__ uint32_t s_mm[KS_WAVES][G::NMM];
-  __shared__ uint32_t s_tkey[KS_WAVES][TCAP];   // resolve table: slot + 1
-  __shared__ uint32_t s_tcnt[KS_WAVES][TCAP];   // hit count (low 16) | root-path score (high 16)
-  __shared__ uint16_t s_tlist[KS_WAVES][WIN ? (int)TCAP : G::MAXN];
-  __shared__ uint32_t s_kk[KS_WAVES][1 << G::KCT_LOG2], s_kc[KS_WAVES][1 << G::KCT_LOG2];
-  __shared__ uint32_t s_rk[KS_WAVES][1 << G::RCT_LOG2], s_rc[KS_WAVES][1 << G::RCT_LOG2];
-  __shared__ uint2 s_hq[KS_WAVES][DO_COUNTS && !ROUTE ? KS_HQ : 1];  // deferred HLL inserts
-  __shared__ uint32_t s_misc[KS_WAVES][4];      // [0] n_kmers table fill, [1] n_reads table fill, [2] list length, [3] WIN: distinct taxa in the table
+  using Lds = KsWaveLds<ITEMS, WIN, !ROUTE, DO_COUNTS && !ROUTE>;
+  __shared__ Lds s_w[KS_WAVES];
 
   const uint32_t lane = threadIdx.x & 63u;
-  // the wave index is uniform: telling the compiler so moves the per-read metadata (r, len, off, n) and the wave's LDS
-  // base addresses to scalar registers and scalar loads
+  // the wave index is uniform: telling the compiler so moves the per-read metadata (r, len, off, n) and the base address of
+  // the wave's LDS block to scalar registers and scalar loads
   const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  uint32_t *codes = s_codes[wv], *amb = s_amb[wv], *mmv = s_mm[wv];
-  uint32_t *t_key = s_tkey[wv], *t_cnt = s_tcnt[wv];
-  uint16_t *t_list = s_tlist[wv];
+  Lds &sw = s_w[wv];
+  uint32_t *codes = sw.codes, *amb = sw.amb, *mmv = sw.mm;
+  uint32_t *t_key = sw.tkey, *t_cnt = sw.tcnt;
+  uint16_t *t_list = sw.tlist;
   uint16_t *amb16 = reinterpret_cast<uint16_t *>(amb);
-  uint32_t *misc = s_misc[wv];
+  uint32_t *misc = sw.misc;
   const uint32_t k = KK ? (uint32_t)KK : db.k, m = KK ? (uint32_t)MM : db.nt, w = k - m + 1;
   const uint32_t key_shift = ku_key_shift(m);
   const uint32_t *tab = reinterpret_cast<const uint32_t *>(db.table);
 
   for (uint32_t i = lane; i < TCAP; i += 64) { t_key[i] = 0; t_cnt[i] = 0; }
   if (!ROUTE)  // (ROUTE: the k-mers are booked by their owners)
-    for (uint32_t i = lane; i < (1u << G::KCT_LOG2); i += 64) { s_kk[wv][i] = 0; s_kc[wv][i] = 0; }
-  for (uint32_t i = lane; i < (1u << G::RCT_LOG2); i += 64) { s_rk[wv][i] = 0; s_rc[wv][i] = 0; }
+    for (uint32_t i = lane; i < (1u << G::KCT_LOG2); i += 64) { sw.kk[i] = 0; sw.kc[i] = 0; }
+  for (uint32_t i = lane; i < (1u << G::RCT_LOG2); i += 64) { sw.rk[i] = 0; sw.rc[i] = 0; }
   if (lane < 4) misc[lane] = 0;
   ks_wave_sync();
 
-  const uint64_t n_waves = (uint64_t)gridDim.x * KS_WAVES;
-#ifdef KS_STAGGER
-  // experiment of round 5 (scripts/build_variant.sh stg -DKS_STAGGER; scripts/rle_depth_probe.py): a launch of the executable's
-  // batch size (61 k reads = 5 per wave) costs 3.6 us per thousand reads against 1.9 for the 10 M-read launch of the bench.
-  // Were the waves of a SIMD held back by marching in step (all in the same stage, waiting for memory together), starting them
-  // (ablate >> 16) * 64 cycles apart would help: measured 4 .. 256 steps, no change (110 ms per 30 M reads every time).  What is
-  // left as an explanation is what a wave pays ONCE -- instruction cache and TLB misses of a kernel of this size on its first
-  // read, the counter tables' flush -- spread over 5 reads instead of 800.
-  {
-    const uint32_t steps = ablate >> 16;
-    const uint32_t slot = ((uint32_t)blockIdx.x / 256u) % 6u;
-    for (uint32_t i = 0; i < slot * steps; ++i) __builtin_amdgcn_s_sleep(1);
-  }
-#endif
+  const uint32_t n_waves = gridDim.x * KS_WAVES;  // (a grid is a few blocks per CU)
   // WIN: this wave's region of the spill workspace (keys, then values), wiped on first use
   uint32_t *g_key = WIN ? spill + ((uint64_t)blockIdx.x * KS_WAVES + wv) * 2ull * spill_cap : nullptr;
   uint32_t *g_cnt = WIN ? g_key + spill_cap : nullptr;
@@ -496,58 +502,23 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
   // instead of one per read.  A read with more than half a queue of them (cold floors, a rare taxon, floor_every = 0) takes
   // the direct way: request all, raise.
   uint32_t hq_fill = 0;  // entries in the queue (wave-uniform)
-  uint2 *hq = s_hq[wv];
-#ifdef KS_PREFETCH
-  // software pipeline over the wave's reads: the text of the NEXT read is requested before the current one is worked
-  // on (its latency hides behind a whole read's worth of work), its length / offset one read earlier still
-  constexpr bool ONE_PASS = (G::NWORDS * 4 + 63) / 64 == 1;
-  uint64_t r_first = (uint64_t)blockIdx.x * KS_WAVES + wv;
-  uint32_t len_n = r_first < n_reads ? seq_len[r_first] : 0;
-  uint64_t off_n = r_first < n_reads ? seq_off[r_first] : 0;
-  uint32_t pre0 = 0, pre1 = 0;
-  bool pre_ok = false;
-  auto prefetch = [&](uint32_t plen, uint64_t poff) {
-    const uint32_t b0 = 4 * lane;
-    const uint64_t a = poff + b0, a0 = a & ~3ull;
-    pre_ok = ONE_PASS && b0 < plen && a0 + 8 <= n_bytes;
-    if (pre_ok) {
-      const uint32_t *q = reinterpret_cast<const uint32_t *>(seqs + a0);
-      pre0 = q[0];
-      pre1 = q[1];
-    }
-  };
-  if (r_first < n_reads) prefetch(len_n, off_n);
-  uint32_t len_nn = r_first + n_waves < n_reads ? seq_len[r_first + n_waves] : 0;
-  uint64_t off_nn = r_first + n_waves < n_reads ? seq_off[r_first + n_waves] : 0;
-#endif
-#ifndef KS_PREFETCH
+  uint2 *hq = reinterpret_cast<uint2 *>(sw.hq);
   uint32_t len_n = 0;
   uint64_t off_n = 0;
   {
     const uint64_t r0 = (uint64_t)blockIdx.x * KS_WAVES + wv;
-    if (r0 < n_reads) { len_n = seq_len[r0]; off_n = seq_off[r0]; }
+    if (ks_less64(r0, n_reads)) { len_n = seq_len[r0]; off_n = seq_off[r0]; }
   }
-#endif
-  for (uint64_t r = (uint64_t)blockIdx.x * KS_WAVES + wv; r < n_reads; r += n_waves) {
-#ifdef KS_PREFETCH
-    const uint32_t rlen = len_n;
-    const uint64_t roff = off_n;
-    const uint32_t cur0 = pre0, cur1 = pre1;
-    const bool cur_ok = pre_ok;
-    len_n = len_nn;
-    off_n = off_nn;
-    if (r + n_waves < n_reads) prefetch(len_n, off_n); else pre_ok = false;
-    if (r + 2 * n_waves < n_reads) { len_nn = seq_len[r + 2 * n_waves]; off_nn = seq_off[r + 2 * n_waves]; }
-#else
+  for (uint64_t r = (uint64_t)blockIdx.x * KS_WAVES + wv; ks_less64(r, n_reads); r += n_waves) {
     // length and offset were requested one read ahead (two scalar loads off the chain of dependent round trips)
     const uint32_t rlen = len_n;
     const uint64_t roff = off_n;
     {
       const uint64_t rn = r + n_waves;
-      len_n = rn < n_reads ? seq_len[rn] : 0u;
-      off_n = rn < n_reads ? seq_off[rn] : 0ull;
+      const bool more = ks_less64(rn, n_reads);
+      len_n = more ? seq_len[rn] : 0u;
+      off_n = more ? seq_off[rn] : 0ull;
     }
-#endif
     // WIN: the read's hit counts so far -- one taxon (rd_first, rd_cnt) until a second one shows up, then the table
     const uint32_t n_all = rlen >= k ? rlen - k + 1 : 0;
     uint32_t rd_first = 0, rd_cnt = 0, win0 = 0;
@@ -567,9 +538,10 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
         ks_floor_scan(cnt.registers, cnt.hll_floor, fl_scan - 1u, lane);
         fl_scan = 0;
       }
-      if (!ROUTE && misc[0] > (1u << G::KCT_LOG2) / 2) ks_ct_flush<G::KCT_LOG2>(s_kk[wv], s_kc[wv], &misc[0], cnt.n_kmers, lane);
+      const uint32_t fill_k = misc[0], fill_r = misc[1];  // (one LDS round trip for both: neither flush touches the other's count)
+      if (!ROUTE && fill_k > (1u << G::KCT_LOG2) / 2) ks_ct_flush<G::KCT_LOG2>(sw.kk, sw.kc, &misc[0], cnt.n_kmers, lane);
       if (!WIN || win0 == 0)
-        if (misc[1] > (1u << G::RCT_LOG2) / 2) ks_rct_flush<G::RCT_LOG2>(s_rk[wv], s_rc[wv], &misc[1], tax, cnt.n_reads, lane);
+        if (fill_r > (1u << G::RCT_LOG2) / 2) ks_rct_flush<G::RCT_LOG2>(sw.rk, sw.rc, &misc[1], tax, cnt.n_reads, lane);
     }
     uint32_t v[ITEMS];  // slot of every k-mer (0 = miss or ambiguous)
     bool amb_k[ITEMS];  // ambiguous k-mer (reported as KU_AMBIG)
@@ -596,30 +568,34 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     } else if (n > 0) {
       // ---- stage 1: ASCII -> 2-bit codes + ambiguity bits in wave-private LDS: four bases per lane (one dword,
       // SWAR), the four lanes of a quad OR their bytes into one 16-base word
+      // Wave-uniform questions are decided once per read (window), in scalar code.  "The read and the two aligned dwords that
+      // cover any four of its bytes lie inside the buffer" is false for the last read(s) of a batch only; everywhere else a
+      // lane fetches its two dwords from the read's aligned base + 4 * lane with no test of its own, and the byte alignment is the
+      // read's, not the lane's.  Lanes behind the read's end fetch its last dword again and mark every base ambiguous.
+      constexpr uint32_t S1_LANES = (uint32_t)((G::NWORDS * 4 + 63) / 64) * 64;
+      // the stores below come from every lane: the four lanes of a quad hold the same word, and a word index behind NWORDS either
+      // still lies inside the arrays (ITEMS = 2) or is clamped to their last element; nothing reads a word behind NWORDS for a
+      // position that belongs to the read
+      constexpr bool S1_CLAMP = S1_LANES / 4 > (uint32_t)G::NCODES || S1_LANES / 4 > 2u * G::NAMB;
+      static_assert(G::NCODES - 1 >= G::NWORDS && 2 * G::NAMB - 1 >= G::NWORDS + 1, "no dump element behind the code words");
+      const bool text_inside = ks_less64(off + len + 6, n_bytes);
+      const uint32_t *text = reinterpret_cast<const uint32_t *>(seqs + (off & ~3ull));
+      const uint32_t text_sh = (uint32_t)off & 3u, last_dw = (len - 1u) & ~3u;
 #pragma unroll
-      for (uint32_t pl = lane; pl < (uint32_t)((G::NWORDS * 4 + 63) / 64) * 64; pl += 64) {
+      for (uint32_t pl = lane; pl < S1_LANES; pl += 64) {
         const uint32_t b0 = 4 * pl;  // first base of this lane
+        const uint32_t valid = len - min(b0, len);  // bases of this dword that belong to the read
         uint32_t c8 = 0, a4 = 0xFu;
-        if (b0 < len) {
+        if (text_inside) {
+          const uint32_t *q = text + (min(b0, last_dw) >> 2);  // two aligned dwords cover the four bytes at any alignment
+          ku_pack_dword(__builtin_amdgcn_alignbyte(q[1], q[0], text_sh), c8, a4);
+        } else if (b0 < len) {
           const uint64_t a = off + b0;
-          const uint64_t a0 = a & ~3ull;
-          uint32_t d;
-#ifdef KS_PREFETCH
-          if (cur_ok && pl == lane && win0 == 0) {
-            d = __builtin_amdgcn_alignbyte(cur1, cur0, (uint32_t)(a & 3ull));
-          } else
-#endif
-          if (a0 + 8 <= n_bytes) {  // two aligned dwords cover the four bytes at any alignment
-            const uint32_t *q = reinterpret_cast<const uint32_t *>(seqs + a0);
-            d = __builtin_amdgcn_alignbyte(q[1], q[0], (uint32_t)(a & 3ull));
-          } else {
-            d = 0;
-            for (uint32_t j = 0; j < 4; ++j) d |= (a + j < n_bytes ? (uint32_t)seqs[a + j] : (uint32_t)'N') << (8 * j);
-          }
+          uint32_t d = 0;
+          for (uint32_t j = 0; j < 4; ++j) d |= (a + j < n_bytes ? (uint32_t)seqs[a + j] : (uint32_t)'N') << (8 * j);
           ku_pack_dword(d, c8, a4);
-          const uint32_t valid = len - b0;  // bases of this dword that belong to the read
-          if (valid < 4) a4 |= (1u << (4 - valid)) - 1u;
         }
+        if (valid < 4) a4 |= (1u << (4 - valid)) - 1u;
         const uint32_t q4 = pl & 3u;
         uint32_t word = c8 << (24 - 8 * q4), ab = a4 << (12 - 4 * q4);
         word |= ku_quad_xor1(word);
@@ -627,10 +603,8 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
         word |= ku_quad_xor2(word);
         ab |= ku_quad_xor2(ab);
         const uint32_t wi = pl >> 2;
-        if (q4 == 0 && wi < (uint32_t)G::NWORDS) {
-          codes[wi] = word;
-          amb16[wi ^ 1u] = (uint16_t)ab;
-        }
+        codes[S1_CLAMP ? min(wi, (uint32_t)G::NCODES - 1u) : wi] = word;
+        amb16[(S1_CLAMP ? min(wi, 2u * G::NAMB - 1u) : wi) ^ 1u] = (uint16_t)ab;
       }
       ks_wave_sync();
 
@@ -644,7 +618,9 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
       uint32_t pk[ITEMS + 1], wr[ITEMS + 1];
       uint32_t tacc = 0xFFFFFFFFu;  // min over the steps of (own ^ neighbour) - 2: < 62 <=> equal keys at two positions
       bool tie = false;             // ... somewhere in the read -> exact scan below
-      if (lane < KS_PAD) mmv[P + lane] = (0x03FFFFFFu - lane) << KU_PK_KEYSHIFT;
+      // (every lane stores one: the array has room for 64 of them behind any P, and the ones past KS_PAD are read by nobody)
+      static_assert(G::MAXN + 30 + 63 < G::NMM - 1, "the sentinels reach the dump slot");
+      mmv[P + lane] = (0x03FFFFFFu - lane) << KU_PK_KEYSHIFT;
       // The k-mers take ITEMS rounds of 64 lanes, the m-mer positions w - 1 more than that: a round of their own when they do not
       // fit ITEMS rounds (a 150 bp read: 138 positions) -- and none when they do (reads up to 140 bp at ITEMS = 2, up to 204 bp at
       // ITEMS = 3: round 6; measured on 100 bp reads: 14.4 -> 14.1 ms per 10 M).
@@ -671,8 +647,9 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
           is_fwd[j] = fwd <= rc;
           canon[j] = is_fwd[j] ? fwd : rc;
           const uint32_t ai = p >> 5, as = p & 31u;
-          const uint64_t a = (((uint64_t)amb[ai] << 32) | amb[ai + 1]) << as;
-          amb_k[j] = p < n && (a >> (64 - k)) != 0;
+          // the k <= 32 ambiguity bits from position p on are the top of one dword: a 32-bit funnel shift and a 32-bit test
+          const uint32_t a = __funnelshift_l(amb[ai + 1], amb[ai], as);
+          amb_k[j] = p < n && (a >> (32 - k)) != 0;
           ok[j] = p < n && !amb_k[j];
         }
       }
@@ -974,8 +951,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     // k-mer; n_kmers per read when the read met one taxon at most (two counter updates instead of one per lane)
     uint32_t n_hit = 0, n_miss = 0;
     if (DO_COUNTS && !ROUTE && n > 0) {
-      uint8_t *reg[ITEMS];
-      uint32_t rank[ITEMS], seen[ITEMS], fl[ITEMS];
+      uint32_t rank[ITEMS], fl[ITEMS];
       if (fl_on && !uni) {  // several taxa: each lane fetches the floors of its own slots
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) fl[j] = ks_gload(&cnt.hll_floor[v[j]]);
@@ -989,16 +965,22 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) {
         const bool okc = j * 64 + lane < n && !amb_k[j];
-        reg[j] = ku_hll_locate(cnt.registers, okc ? v[j] : 0u, hh[j], rank[j]);
+        (void)ku_hll_locate(cnt.registers, 0u, hh[j], rank[j]);  // (the rank alone: a register's address is formed on the direct way only)
         go[j] = okc && rank[j] > fl[j] && !KS_ABL(2u);
         gob[j] = __ballot(go[j]);
         n_go += (uint32_t)__popcll(gob[j]);
       }
       const bool direct = !fl_on || n_go > KS_HQ / 2;  // wave-uniform
       if (direct) {
+        uint8_t *reg[ITEMS];
+        uint32_t seen[ITEMS];
 #pragma unroll
-        for (int j = 0; j < ITEMS; ++j)  // every register byte is requested before the first one is looked at
+        for (int j = 0; j < ITEMS; ++j) {  // every register byte is requested before the first one is looked at
+          reg[j] = ku_hll_locate(cnt.registers, go[j] ? v[j] : 0u, hh[j], rank[j]);
           seen[j] = go[j] ? (uint32_t)*reg[j] : 0xFFu;  // (0xFF: nothing to raise)
+        }
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) ku_hll_raise(reg[j], seen[j], rank[j]);
       } else {
         if (hq_fill + n_go > KS_HQ) {
           ks_hq_drain(hq, hq_fill, cnt.registers, lane);
@@ -1009,23 +991,21 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
           const uint32_t at = hq_fill + __builtin_amdgcn_mbcnt_hi((uint32_t)(gob[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)gob[j], 0u));
           if (go[j]) hq[at] = make_uint2(v[j], (uint32_t)(hh[j] >> (64 - KU_HLL_P)) | (rank[j] << KU_HLL_P));
           hq_fill += (uint32_t)__popcll(gob[j]);
-          seen[j] = 0xFFu;
         }
       }
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) {
         const bool okc = j * 64 + lane < n && !amb_k[j];
-        ku_hll_raise(reg[j], seen[j], rank[j]);
         if (uni) {
           n_hit += (uint32_t)__popcll(__ballot(okc && v[j] != 0));
           n_miss += (uint32_t)__popcll(__ballot(okc && v[j] == 0));
         } else if (okc && !KS_ABL(4u)) {
-          ku_ct_add<G::KCT_LOG2>(s_kk[wv], s_kc[wv], &misc[0], v[j], 1, cnt.n_kmers);
+          ku_ct_add<G::KCT_LOG2>(sw.kk, sw.kc, &misc[0], v[j], 1, cnt.n_kmers);
         }
       }
       if (uni && lane == 0 && !KS_ABL(4u)) {
-        if (n_hit) ku_ct_add<G::KCT_LOG2>(s_kk[wv], s_kc[wv], &misc[0], uni_slot, n_hit, cnt.n_kmers);
-        if (n_miss) ku_ct_add<G::KCT_LOG2>(s_kk[wv], s_kc[wv], &misc[0], 0u, n_miss, cnt.n_kmers);
+        if (n_hit) ku_ct_add<G::KCT_LOG2>(sw.kk, sw.kc, &misc[0], uni_slot, n_hit, cnt.n_kmers);
+        if (n_miss) ku_ct_add<G::KCT_LOG2>(sw.kk, sw.kc, &misc[0], 0u, n_miss, cnt.n_kmers);
       }
       if (fl_on && ((++fl_reads) & 0x7fffffffu) >= floor_every) {  // a scan is due: the turn changes, the count starts again
         fl_reads = ~fl_reads & 0x80000000u;
@@ -1142,7 +1122,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
         calls[r] = uni ? uni_code : tax.node_taxid[call_node];
         // incrementReadCount (classify.cpp:968): per node; single-taxon reads are booked under their slot and become
         // nodes when the wave's table is flushed
-        if (DO_COUNTS) ks_rct_add<G::RCT_LOG2>(s_rk[wv], s_rc[wv], &misc[1], uni ? (KS_RCT_SLOT | uni_slot) : call_node, tax, cnt.n_reads);
+        if (DO_COUNTS) ks_rct_add<G::RCT_LOG2>(sw.rk, sw.rc, &misc[1], uni ? (KS_RCT_SLOT | uni_slot) : call_node, tax, cnt.n_reads);
       }
       ks_wave_sync();  // the next read reuses the wave's LDS arrays
       break;
@@ -1192,7 +1172,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
           ro.run_off[r] = run_base;
           ro.run_cnt[r] = run_n;
         }
-        if (DO_COUNTS) ks_rct_add<G::RCT_LOG2>(s_rk[wv], s_rc[wv], &misc[1], rd_table ? call_node : (KS_RCT_SLOT | rd_first), tax, cnt.n_reads);
+        if (DO_COUNTS) ks_rct_add<G::RCT_LOG2>(sw.rk, sw.rc, &misc[1], rd_table ? call_node : (KS_RCT_SLOT | rd_first), tax, cnt.n_reads);
       }
       ks_wave_sync();
     }
@@ -1200,17 +1180,18 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
 #ifndef KS_DIAG_NOFLUSH  // (diagnostic builds: what do the waves' last flushes cost a small launch?  scripts/launch_shape_probe.py)
   if (DO_COUNTS) {
     // the counters every wave holds -- misses (slot 0), reads without a hit (node 0) -- leave the block as ONE add each
-    __shared__ uint32_t s_hot[KS_WAVES][2];
-    if (lane < 2) s_hot[wv][lane] = 0;
+    // (in misc[2] and [3]: the resolve list and the windowed table are done with)
+    ks_wave_sync();
+    if (lane < 2) misc[2 + lane] = 0;
     if (!ROUTE && hq_fill) ks_hq_drain(hq, hq_fill, cnt.registers, lane);
     if (!ROUTE && fl_scan) ks_floor_scan(cnt.registers, cnt.hll_floor, fl_scan - 1u, lane);
-    if (!ROUTE) ks_ct_flush<G::KCT_LOG2>(s_kk[wv], s_kc[wv], &misc[0], cnt.n_kmers, lane, &s_hot[wv][0]);
-    ks_rct_flush<G::RCT_LOG2>(s_rk[wv], s_rc[wv], &misc[1], tax, cnt.n_reads, lane, &s_hot[wv][1]);
+    if (!ROUTE) ks_ct_flush<G::KCT_LOG2>(sw.kk, sw.kc, &misc[0], cnt.n_kmers, lane, &misc[2]);
+    ks_rct_flush<G::RCT_LOG2>(sw.rk, sw.rc, &misc[1], tax, cnt.n_reads, lane, &misc[3]);
     __syncthreads();  // (every wave of the block reaches the end of the kernel: the only block barrier in it)
     if (wv == 0 && lane < 2) {
       unsigned long long sum = 0;
 #pragma unroll
-      for (int q = 0; q < KS_WAVES; ++q) sum += s_hot[q][lane];
+      for (int q = 0; q < KS_WAVES; ++q) sum += s_w[q].misc[2 + lane];
       if (sum) atomicAdd(lane == 0 ? &cnt.n_kmers[0] : &cnt.n_reads[0], sum);
     }
   }
