@@ -385,6 +385,18 @@ void ctx_free_sparse(ku_ctx *ctx) {
     b->release();
   ctx->sp = ku_ctx::Sparse{};
 }
+// The emulation ran out of device memory: it is given up, the run goes on with the dense registers alone and says so
+// (ku_ctx_sparse_state: 2; the classification itself does not depend on the emulation's tables).  The rule this enforces:
+// nothing may still be queued that reads or writes the emulation's tables when they are freed -- the kernels of the batches
+// in flight do both -- so every stream of the context is waited for, and `also` when a stream of the caller's was in use.
+int sparse_give_up(ku_ctx *ctx, hipStream_t also) {
+  (void)ctx_sync_all_streams(ctx);
+  if (also) (void)hipStreamSynchronize(also);
+  (void)hipGetLastError();
+  ctx_free_sparse(ctx);
+  ctx->sp.gave_up = true;
+  return KU_OK;
+}
 static void ctx_free_tax(ku_ctx *ctx) {
   for (uint32_t **p : {&ctx->d_node_parent, &ctx->d_node_slot, &ctx->d_node_taxid, &ctx->d_slot_node, &ctx->d_slot_taxid,
                        &ctx->d_slot_anc_off, &ctx->d_slot_anc}) {
@@ -429,7 +441,6 @@ extern "C" void ku_ctx_destroy(ku_ctx *ctx) {
   if (ctx->d_scalar) (void)hipFree(ctx->d_scalar);
   if (ctx->pf.d_scalar) (void)hipFree(ctx->pf.d_scalar);
   if (ctx->pf.stream) (void)hipStreamDestroy(ctx->pf.stream);
-  for (hipEvent_t e : ctx->seg_events) (void)hipEventDestroy(e);
   for (RleJob &j : ctx->rle) j.release();
   if (ctx->h2d_stream) (void)hipStreamDestroy(ctx->h2d_stream);
   if (ctx->d2h_stream) (void)hipStreamDestroy(ctx->d2h_stream);

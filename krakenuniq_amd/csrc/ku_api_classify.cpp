@@ -53,7 +53,7 @@ int ku_ctx_route_resolve_prepare(ku_ctx *ctx, const ku_opts *opts, hipStream_t s
   const uint32_t flags = opts ? opts->flags : 0;
   const uint32_t max_len = opts ? opts->max_read_len : 0;
   if (max_len == 0 || (flags & (KU_F_QUICK | KU_F_KEEP_SLOTS)) || getenv("KU_NO_FUSED")) return KU_EUNSUP;  // (no message: the caller has another path)
-  const uint32_t max_n = max_len >= ctx->m.db.k ? max_len - ctx->m.db.k + 1 : 0;
+  const uint32_t max_n = ku_max_kmers(ctx->m.db.k, max_len);
   if (max_n > ku_route_resolve_max_kmers()) return KU_EUNSUP;
   if (max_n > 128) {
     const uint64_t ws = ku_short_workspace_bytes(std::max(max_n, 193u), ctx->tax.n_slots, ~0ull >> 8, ctx->n_cu);
@@ -68,7 +68,7 @@ int ku_ctx_route_resolve(ku_ctx *ctx, const uint64_t *d_off, const uint32_t *d_l
                          uint32_t *d_taxa, uint32_t *d_hits, const uint32_t *d_kb, const uint32_t *d_ret, hipStream_t s) {
   const uint32_t flags = opts ? opts->flags : 0;
   const uint32_t max_len = opts ? opts->max_read_len : 0;
-  const uint32_t max_n = max_len >= ctx->m.db.k ? max_len - ctx->m.db.k + 1 : 0;
+  const uint32_t max_n = ku_max_kmers(ctx->m.db.k, max_len);
   int st = ku_launch_route_resolve(ctx->m.db, ctx->tax, ctx->cnt, d_off, d_len, n_reads, max_n, flags, d_calls, d_taxa, d_hits, d_kb, d_ret,
                                    ctx->b_ws.p, ctx->b_ws.cap, ctx->n_cu, s);
   return st == KU_OK ? KU_OK : fail(st, "routed resolve kernel launch failed");
@@ -162,7 +162,7 @@ int classify_device_impl(ku_ctx *ctx, const void *d_seqs, uint64_t n_bytes, cons
       HIP_TRY(hipMemcpyAsync(&max_len, ctx->d_scalar + 4, 4, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
     }
-    const uint32_t max_n = max_len >= ctx->m.db.k ? max_len - ctx->m.db.k + 1 : 0;
+    const uint32_t max_n = ku_max_kmers(ctx->m.db.k, max_len);
     // longer reads (mate pairs, long reads up to 65535 k-mers): the same kernel in windows of 128 k-mers -- when its
     // spill workspace can be had; KU_NO_WINDOWED=1 keeps them on the flat lookup + resolve kernels
     bool fused = max_n <= short_max;
@@ -189,10 +189,7 @@ int classify_device_impl(ku_ctx *ctx, const void *d_seqs, uint64_t n_bytes, cons
     if (st == KU_ENOMEM) {
       // no room for the emulation's tables: the classification itself does not depend on them -- the run goes on with
       // the dense registers alone and says so (ku_ctx_sparse_state; the reports then carry their estimates)
-      (void)hipStreamSynchronize(stream ? (hipStream_t)stream : ctx->stream);
-      (void)hipGetLastError();
-      ctx_free_sparse(ctx);
-      ctx->sp.gave_up = true;
+      sparse_give_up(ctx, (hipStream_t)stream);
     } else if (st != KU_OK) return st;
   }
   if (exact) {  // between the stages: d_taxa holds slot ids

@@ -196,12 +196,8 @@ extern "C" int ku_batch_finish(ku_ctx *ctx, ku_batch *b, const ku_opts *opts, ui
   if (ctx->sp.on && !(o.flags & KU_F_NO_COUNTS)) {  // the merged slots of all chunks are in place: the emulation's pass
     if (b->h_len.size() != n_reads) return fail(KU_ESTATE, "ku_batch_finish: enable the sparse-mode emulation before the batches are created");
     int sst = sparse_pass(ctx, b->d_seqs, b->d_off, b->d_len, b->h_off.data(), b->h_len.data(), n_reads, b->n_bytes, b->d_taxa, 0u, s);
-    if (sst == KU_ENOMEM) {  // as in classify_device_impl: the run goes on without the emulation
-      (void)hipStreamSynchronize(s);
-      (void)hipGetLastError();
-      ctx_free_sparse(ctx);
-      ctx->sp.gave_up = true;
-    } else if (sst != KU_OK) return sst;
+    if (sst == KU_ENOMEM) sparse_give_up(ctx);  // as in classify_device_impl: the run goes on without the emulation
+    else if (sst != KU_OK) return sst;
   }
   if (ctx->d_exact_set && !(o.flags & KU_F_NO_COUNTS)) {
     // exact counting of a chunked run: the merged slots of all chunks are in place, and a chunked run books every k-mer of

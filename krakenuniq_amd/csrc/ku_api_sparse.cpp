@@ -277,14 +277,7 @@ int ku_ctx_sparse_pass_slots(ku_ctx *ctx, const void *d_seqs, const uint64_t *d_
   KU_TRY(check_ready(ctx));
   if (!ctx->sp.on || n_reads == 0) return KU_OK;
   int st = sparse_pass(ctx, d_seqs, d_off, d_len, h_off, h_len, n_reads, n_bytes, d_taxa, quick_min_hits, s);
-  if (st == KU_ENOMEM) {
-    (void)hipStreamSynchronize(s);
-    (void)hipGetLastError();
-    ctx_free_sparse(ctx);
-    ctx->sp.gave_up = true;
-    return KU_OK;
-  }
-  return st;
+  return st == KU_ENOMEM ? sparse_give_up(ctx, s) : st;
 }
 // the unit that is still open on `src` continues on `dst` (same process; the contexts may sit on different devices)
 int ku_ctx_sparse_move_open_unit(ku_ctx *src, ku_ctx *dst) {

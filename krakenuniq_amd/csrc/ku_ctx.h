@@ -1,9 +1,10 @@
 // ku_ctx.h -- what the translation units of the C ABI share (ku_api*.cpp): the objects behind the opaque handles of
 // include/krakenuniq_amd.h, the error helpers, and the few functions one area calls in another.
-//   ku_api.cpp           errors, ku_db / ku_tax, the context: create / destroy, database load + probe table, taxonomy, reset
+//   ku_api.cpp           errors, ku_db / ku_tax, the context: create / destroy, database load + probe table, taxonomy, reset, giving the emulation up
 //   ku_api_sparse.cpp    HyperLogLog++ sparse-mode emulation: state, staged passes, export, the group's view
 //   ku_api_classify.cpp  lookup / resolve / classify entry points on device and host buffers, owner routing
-//   ku_api_rle.cpp       the host-batch call with run-length encoded output, in one step and in two (batches in flight)
+//   ku_api_rle.cpp       the host-batch call with run-length encoded output, in one step and in two (batches in flight): the
+//                        batch plan, the staged enqueue, finish, warm-up, KU_RLE_TIMES
 //   ku_api_ooc.cpp       out-of-core runs: chunk swap / prefetch, device-resident batches, merging contexts
 //   ku_api_report.cpp    counts export, the report from the resident state
 #pragma once
@@ -44,6 +45,12 @@ static inline int fail(int code, const std::string &msg) {
     int s_ = (expr);            \
     if (s_ != KU_OK) return s_; \
   } while (0)
+
+// streams and events that are created on first use
+static inline int ensure_stream(hipStream_t &s) { if (!s) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return KU_OK; }
+static inline int ensure_event(hipEvent_t &e, unsigned flags = hipEventDisableTiming) { if (!e) HIP_TRY(hipEventCreateWithFlags(&e, flags)); return KU_OK; }
+// k-mers of a read of `len` bases
+static inline uint32_t ku_max_kmers(uint32_t k, uint32_t len) { return len >= k ? len - k + 1 : 0; }
 
 struct ku_db {
   const uint8_t *pairs = nullptr;
@@ -92,11 +99,27 @@ struct PinBuf {
   void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
+// What the caller hands to ku_classify_batch_rle_enqueue: the reads, the options as the entry point completed them, and where
+// the results go on the host.
+struct RleBatch {
+  const char *seqs;
+  uint64_t n_bytes;
+  const uint64_t *seq_off;
+  const uint32_t *seq_len;
+  uint64_t n_reads;
+  ku_opts o;
+  uint32_t max_n;   // k-mers of the longest read
+  bool monotonic;   // the reads lie in the buffer in their order, without overlap
+  uint32_t *calls, *hits, *run_cnt;
+  uint64_t *run_off;
+  ku_run *runs;     // optional: the runs come with the other results, as many as runs_cap holds
+  uint64_t runs_cap;
+};
+
 // One batch on its way through the fused kernel with run-length encoded output (ku_classify_batch_rle_enqueue / _finish,
 // round 5): its own device buffers and page-locked scratch -- KU_RLE_MAX_IN_FLIGHT of them take turns, so that the uploads of
 // the next batches and the copies back of the previous ones run under the kernel of batch b and the host waits for ONE event
-// per batch -- and what
-// _finish needs to know about the batch.
+// per batch -- and what _finish needs to know about the batch.
 struct RleJob {
   DevBuf seqs, off, len, calls, runs, roff, rcnt, ws, unit, u_cnt, u_flag;
   PinBuf pin;       // [0] extent of the run array, [1] entries of the run-wide set, [2] the emulation's error word; byte 64 on: unit flags
@@ -110,13 +133,8 @@ struct RleJob {
   bool runs_in_ctx = false;     // the runs lie in the context's own run buffer (one-step paths, the overflow redo)
   uint64_t runs_copied = 0;     // entries of the run array already copied to the caller's buffer (0: ku_fetch_runs does it)
   uint64_t n_runs = 0;
-  // the batch
-  uint64_t n_bytes = 0, n_reads = 0, runs_cap = 0;
-  uint32_t max_n = 0;
-  ku_opts o{};
-  const uint32_t *h_len = nullptr;
-  uint32_t *h_calls = nullptr, *h_hits = nullptr, *h_rcnt = nullptr;
-  uint64_t *h_roff = nullptr;
+  RleBatch b{};                 // the batch
+  uint64_t runs_cap = 0;        // entries of its run array on the device (b.runs_cap: of the caller's buffer)
   // sparse-sketch emulation, fast path: the batch's work units
   bool sparse = false;
   bool cont_carry = false;      // unit 0 continues a unit whose state sits in the carry buffers (L / U entries; the staged form)
@@ -128,16 +146,29 @@ struct RleJob {
   std::vector<uint64_t> unit_first_read;
   std::vector<char> tail_text;      // cont_tail: the reads of the open unit BEFORE this batch (bases, each read followed by '\n')
   std::vector<uint32_t> tail_len;
+  // The job's buffers and events for a batch of these sizes (units: the emulation's work units, when it is on): _enqueue asks
+  // for what its batch needs, _reserve for upper bounds ahead of the first batch.
+  int reserve(uint64_t n_bytes, uint64_t n_reads, uint64_t runs_cap_, uint64_t ws_bytes, size_t n_seg, bool sparse_, uint64_t units, uint64_t n_slots) {
+    if (seqs.reserve(n_bytes + 16) || off.reserve(n_reads * 8) || len.reserve(n_reads * 4) || calls.reserve(n_reads * 4) ||
+        runs.reserve(runs_cap_ * 8) || roff.reserve(n_reads * 8) || rcnt.reserve(n_reads * 4) || ws.reserve(ws_bytes))
+      return fail(KU_ENOMEM, "device batch buffers");
+    units = std::max<uint64_t>(units, 1);
+    if (sparse_ && (pin_unit.reserve(n_reads * 4) || unit.reserve(n_reads * 4) || u_cnt.reserve(std::max<uint64_t>(units * n_slots, 1) * 4) ||
+                    u_flag.reserve((units + 3) & ~3ull)))
+      return fail(KU_ENOMEM, "device memory for the work-unit counters");
+    if (pin.reserve(64 + (size_t)units + 64)) return fail(KU_ENOMEM, "page-locked memory for the batch totals");
+    KU_TRY(ensure_event(done));
+    KU_TRY(ensure_event(kernels_done));
+    seg_events.resize(std::max(seg_events.size(), n_seg), nullptr);
+    for (hipEvent_t &e : seg_events) KU_TRY(ensure_event(e));
+    return KU_OK;
+  }
   void release() {
-    for (DevBuf *b : {&seqs, &off, &len, &calls, &runs, &roff, &rcnt, &ws, &unit, &u_cnt, &u_flag}) b->release();
+    for (DevBuf *d : {&seqs, &off, &len, &calls, &runs, &roff, &rcnt, &ws, &unit, &u_cnt, &u_flag}) d->release();
     pin.release();
     pin_unit.release();
-    if (kernels_done) (void)hipEventDestroy(kernels_done);
-    if (done) (void)hipEventDestroy(done);
-    if (t_k0) (void)hipEventDestroy(t_k0);
-    if (t_k1) (void)hipEventDestroy(t_k1);
-    for (hipEvent_t e : seg_events) (void)hipEventDestroy(e);
-    kernels_done = done = t_k0 = t_k1 = nullptr;
+    for (hipEvent_t *e : {&kernels_done, &done, &t_k0, &t_k1}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    for (hipEvent_t e : seg_events) if (e) (void)hipEventDestroy(e);
     seg_events.clear();
   }
 };
@@ -190,9 +221,8 @@ struct ku_ctx {
   hipStream_t k_streams[2] = {nullptr, nullptr};
   hipEvent_t main_ev = nullptr;
   hipEvent_t prev_kernels_done = nullptr;  // (a job's event, not owned)
-  std::vector<hipEvent_t> seg_events;
   uint32_t *d_scalar = nullptr;
-  // ku_classify_batch_rle in two steps: up to two batches in flight (FIFO: rle_head is the oldest)
+  // ku_classify_batch_rle in two steps: up to KU_RLE_MAX_IN_FLIGHT batches in flight (FIFO: rle_head is the oldest)
   RleJob rle[KU_RLE_MAX_IN_FLIGHT];
   int rle_head = 0, rle_in_flight = 0;
   const void *fetch_runs_src = nullptr;  // where the runs of the batch finished last lie (ku_fetch_runs)
@@ -261,6 +291,7 @@ int ctx_sync_all_streams(ku_ctx *ctx);  // ku_api.cpp
 void store_free(DbStore &d);  // ku_api.cpp
 void ctx_drop_count_cache(ku_ctx *ctx);  // ku_api.cpp
 void ctx_free_sparse(ku_ctx *ctx);  // ku_api.cpp
+int sparse_give_up(ku_ctx *ctx, hipStream_t also = nullptr);  // ku_api.cpp
 int store_upload(ku_ctx *ctx, DbStore &d, const ku_db *db, uint64_t bin_lo, uint64_t bin_hi, bool scan_values = true, hipStream_t stream = nullptr);  // ku_api.cpp
 bool store_whole(const DbStore &d);  // ku_api.cpp
 int store_finalize(ku_ctx *ctx, DbStore &d, hipStream_t stream = nullptr, uint32_t *d_scalar = nullptr);  // ku_api.cpp

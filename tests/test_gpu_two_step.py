@@ -30,8 +30,9 @@ def batches_of(buf, off, lens, cuts):
         yield a, b, buf[lo:hi], off[a:b] - lo, lens[a:b]
 
 
-def run_two_step(ctx, buf, off, lens, cuts, depth=3, **kw):
-    """every batch through enqueue / finish with up to `depth` in flight; results in batch order"""
+def run_two_step(ctx, buf, off, lens, cuts, depth=3, after_enqueue=None, **kw):
+    """every batch through enqueue / finish with up to `depth` in flight; results in batch order
+    (after_enqueue(i): called behind the enqueue of batch i, while it is in flight)"""
     flying, out = [], []
     for i, (a, b, bb, bo, bl) in enumerate(batches_of(buf, off, lens, cuts)):
         if len(flying) >= depth:
@@ -40,6 +41,8 @@ def run_two_step(ctx, buf, off, lens, cuts, depth=3, **kw):
         # (they come with the calls)
         flying.append(ctx.rle_enqueue(bb, bo, bl, runs_cap=(0, 3, 1 << 16)[i % 3], **kw))
         assert ctx.rle_in_flight() == len(flying)
+        if after_enqueue:
+            after_enqueue(i)
     while flying:
         out.append(ctx.rle_finish(flying.pop(0)))
     assert ctx.rle_in_flight() == 0
@@ -183,6 +186,61 @@ def test_reserve_and_its_warm_up_change_nothing(monkeypatch):
         states.append((text, c["n_reads"].copy(), c["n_kmers"].copy(), c["registers"].copy()))
     for t, a, b, r in states[1:]:
         assert t == states[0][0] and np.array_equal(a, states[0][1]) and np.array_equal(b, states[0][2]) and np.array_equal(r, states[0][3])
+
+
+def giveup_cuts(case, n):
+    if case == "at_the_first_enqueue":
+        return split_points(n, 9, 8)
+    return [0, 20, 40] + [60 + c for c in split_points(n - 60, 6, 8)]
+
+
+@pytest.mark.parametrize("case,max_log2,global_log2,gives_up_at", [("at_the_first_enqueue", 11, 10, 0), ("behind_three_batches", 15, 12, 3)])
+def test_emulation_gives_up_with_batches_in_flight(case, max_log2, global_log2, gives_up_at, monkeypatch):
+    """test_gpu_sparse's out-of-memory case through the two-step call at depth 3 (KU_SPARSE_MAX_LOG2: a ceiling for the
+    run-wide set stands in for a full device).
+
+    at_the_first_enqueue: a ceiling of 2^11 cells and nine batches.  The first batch alone (176 reads, 21 120 k-mers) outgrows
+    the ceiling, so the emulation goes before anything is queued: the one-step test's outcome through the other calling sequence.
+
+    behind_three_batches: three leading batches of 20 reads (2 400 k-mers each) fit under a ceiling of 2^15 cells whatever
+    the set holds (at most 2 * (4 800 + 7 200) = 24 000 cells asked for); the fourth (166 reads, 19 920 k-mers, two batches in
+    flight ahead of it) asks for at least 49 440.  So the emulation is given up by an _enqueue while two batches that were
+    queued with it ON are in flight, and they are finished with it OFF.
+
+    Both: classification is untouched, the state says 2, the report is the dense-register one, and the per-taxon state is that
+    of a run that never had the emulation on.
+
+    NOT covered: tables freed while kernels of batches in flight still run.  Every give-up the ceiling can provoke comes from
+    sparse_reserve_global, which waits for the batches in flight (rle_drain_batches) before it refuses; the fused kernel cannot
+    fill the set, whose room is reserved from upper bounds.  That sparse_give_up waits for every stream is by reading only."""
+    ids, seqs = synth.read_seqfile(f"{F1}/reads.fq")
+    buf, off, lens = ko.pack_reads(seqs)
+    cuts = giveup_cuts(case, len(seqs))
+    monkeypatch.setenv("KU_SPARSE_MAX_LOG2", str(max_log2))
+    ctx, cdb, ctax = gc.make_ctx(F1)
+    ctx.enable_sparse(1000, global_log2)
+    assert ctx.sparse_state() == 1
+    seen = {}
+
+    def after_enqueue(i):
+        seen[i] = (ctx.sparse_state(), ctx.rle_in_flight())
+
+    res = run_two_step(ctx, buf, off, lens, cuts, depth=3, after_enqueue=after_enqueue)
+    print(case, seen)
+    # on until the enqueue that gives it up, with as many batches in flight as the depth allows; off from there
+    want_in_flight = min(gives_up_at + 1, 3)
+    assert all(seen[i] == (1, min(i + 1, 3)) for i in range(gives_up_at)), seen
+    assert seen[gives_up_at] == (2, want_in_flight), seen
+    assert ctx.sparse_state() == 2
+    assert ctx.rle_in_flight() == 0
+    assert kraken_text(buf, off, lens, ids, cuts, res) == open(f"{F1}/out.tsv").read()
+    paths = [f"{F1}/database.kdb.counts"]
+    assert ctx.report(ctax, paths) == capi.report(ctax, ctx.counts(), paths)
+    ctx2, _, _ = gc.make_ctx(F1)
+    run_two_step(ctx2, buf, off, lens, cuts, depth=3)
+    c1, c2 = ctx.counts(), ctx2.counts()
+    for key in ("n_kmers", "registers", "n_reads"):
+        assert np.array_equal(c1[key], c2[key]), key
 
 
 @pytest.mark.parametrize("unit,report,n_batches", [(1000, "report_u1000.tsv", 9), (500000, "report.tsv", 7), (7000, None, 12)])
