@@ -75,7 +75,7 @@ def merge_taxa_max(taxa_i32: torch.Tensor) -> torch.Tensor:
 
 
 def exchange_slices_max(taxa_i32: torch.Tensor, pos) -> torch.Tensor:
-    """the sharded step's reduce-scatter as the C++ driver does it over xGMI (comm_reduce_slices_max, ku_mgpu.cpp): an
+    """the sharded step's reduce-scatter as the C++ driver does it over xGMI (comm_reduce_slices_max, ku_mgpu_comm.h): an
     all-to-all of point-to-point transfers -- slice q = [pos[q], pos[q+1]) of every rank's array goes straight to rank q,
     which folds the world-1 slices it receives into its own with a max.  In place; afterwards this rank's slice holds
     the merged slots (the other slices keep the local values)."""
@@ -104,7 +104,7 @@ def exchange_slices_max(taxa_i32: torch.Tensor, pos) -> torch.Tensor:
 
 
 def alltoallv(send: list, dtype=torch.int64) -> list:
-    """the routed step's variable all-to-all as the C++ driver does it (comm_allgather_u64 + comm_alltoallv, ku_mgpu.cpp):
+    """the routed step's variable all-to-all as the C++ driver does it (comm_allgather_u64_dev + comm_alltoallv, ku_mgpu_comm.h):
     the per-owner counts are all-gathered so that every rank knows how much it gets from whom, then queue q of every rank
     goes straight to rank q by point-to-point transfers.  send[q]: 1-D tensor for rank q; returns recv[q] from rank q."""
     rank, ws = world()
@@ -130,7 +130,7 @@ def alltoallv(send: list, dtype=torch.int64) -> list:
 
 
 def route_lookup(kmers_i64: torch.Tensor, owner: torch.Tensor, probe) -> torch.Tensor:
-    """owner routing of one rank's slice (rank_step_routed, ku_mgpu.cpp): the unambiguous k-mers of the slice (kmers_i64, in
+    """owner routing of one rank's slice (RoutedStep, ku_mgpu_route.h): the unambiguous k-mers of the slice (kmers_i64, in
     scan order) go to the rank that owns their bin (owner[i]), probe(k-mers received) -> slots runs THERE (with the
     owner's accounting as a side effect), the slots come back and are scattered into scan order."""
     _, ws = world()

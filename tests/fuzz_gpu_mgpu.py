@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Extended differential run on a GPU box (not collected by pytest; `python tests/fuzz_gpu_mgpu.py [cases] [first_seed]`): the
-multi-GPU driver (ku_mgpu.cpp) with 2-6 ranks on one device -- minimizer-range shards with owner routing (also with queues too
+multi-GPU driver (ku_mgpu.cpp, ku_mgpu_comm.h, ku_mgpu_route.h) with 2-6 ranks on one device -- minimizer-range shards with owner routing (also with queues too
 small for the first pass and with rounds cut inside reads), the position-wise exchange, replicas -- on random databases
 (k, nt, taxonomy), reads of very different abundance per taxon, random work-unit sizes and batch cuts, the sparse-sketch
 emulation on: calls, per-taxon counts and registers, which sketches stayed sparse and their exact sets against the oracle after

@@ -1,4 +1,5 @@
-"""-m gpu: the C++ multi-GPU driver (ku_mgpu, krakenuniq_amd/csrc/ku_mgpu.cpp) through the C ABI.
+"""-m gpu: the C++ multi-GPU driver (ku_mgpu: krakenuniq_amd/csrc/ku_mgpu.cpp over ku_mgpu_comm.h, ku_route_plan.h and
+ku_mgpu_route.h) through the C ABI.
 
 A 1-GPU box runs several ranks on its one device (same-process exchange: device copies + merge kernels); boxes with
 more devices also take the RCCL exchange.  Every variant has to reproduce the single-context results: the reference's
@@ -117,6 +118,33 @@ def test_empty_and_tiny_batches(f1):
     r = mg.classify_batch_rle(f1["buf"][:cut], f1["off"][:2], f1["lens"][:2])
     assert capi.format_kraken_rle(f1["buf"][:cut], f1["off"][:2], f1["lens"][:2], f1["ids"][:2], K, r) == \
         "".join(f1["text"].splitlines(True)[:2])
+    mg.close()
+
+
+def test_device_step_with_a_null_buffer_on_one_rank_is_refused_before_any_rank_starts(f1):
+    """ku_mgpu_step_device with rank 1's d_taxa null: KU_EINVAL from the check in front of the ranks' threads (a rank that
+    found it out alone, in its thread, used to leave and rank 0 waited in its first barrier for ever), and the group
+    classifies the next batch as if nothing had happened"""
+    import torch
+    dev = torch.device("cuda:0")
+    mg = capi.Mgpu([0, 0])
+    mg.load(f1["cdb"], f1["ctax"])
+    nb, n = len(f1["buf"]), len(f1["lens"])
+    seqs = torch.zeros(nb + 16, dtype=torch.uint8, device=dev)
+    off = torch.zeros(n, dtype=torch.int64, device=dev)
+    lens = torch.zeros(n, dtype=torch.int32, device=dev)
+    calls = torch.zeros(n, dtype=torch.int32, device=dev)
+    taxa = torch.zeros(nb + 16, dtype=torch.int32, device=dev)
+    batches = [{"d_seqs": seqs.data_ptr(), "d_seq_off": off.data_ptr(), "d_seq_len": lens.data_ptr(), "d_calls": calls.data_ptr(),
+                "d_taxa": taxa.data_ptr() if r == 0 else None} for r in range(2)]
+    h = n // 2
+    with pytest.raises(capi.KuError) as e:
+        mg.step_device(batches, nb, n, [0, h, n], [0, int(f1["off"][h]), nb])
+    assert e.value.status == -1  # KU_EINVAL
+    rle = mg.classify_batch_rle(f1["buf"], f1["off"], f1["lens"])
+    assert capi.format_kraken_rle(f1["buf"], f1["off"], f1["lens"], f1["ids"], K, rle) == f1["text"]
+    mg.reduce_state()
+    assert same_counts(mg.ctx(1).counts(), f1["counts"])
     mg.close()
 
 
