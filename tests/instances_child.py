@@ -326,7 +326,10 @@ def route_cells(out, tmp):
     offs = db.offsets
     bounds = [0] + [int(torch.searchsorted(offs, offs[-1] * q // W).item()) for q in range(1, W)] + [4 ** NT]
     for cell in ki.MATRIX["route"]:
-        shape, cnt = cell.split("/")[1], cell.split("/")[3]
+        group, shape, cnt = cell.split("/")[0], cell.split("/")[1], cell.split("/")[3]
+        if group != "route":
+            route_geometry_cell(out, cell, int(group[5:]), cnt)
+            continue
         try:
             if shape == "s128":
                 N, L = 20_000, 150
@@ -386,6 +389,36 @@ def route_cells(out, tmp):
             torch.cuda.empty_cache()
         except Exception:
             out.fail(cell, traceback.format_exc(limit=6))
+
+
+_route_worlds = {}
+
+
+def route_geometry_cell(out, cell, nt, cnt):
+    """route13 / route15: the routed step at k = 31, nt = 13 / 15 over two narrow bin ranges (route_geometry.py)"""
+    from krakenuniq_amd import capi
+    import route_geometry as rg
+    try:
+        if nt not in _route_worlds:
+            w = rg.World(31, nt)
+            reads = rg.make_reads(w, "short", 1)
+            _route_worlds[nt] = (w, reads, rg.Reference(w, reads))
+        w, reads, ref = _route_worlds[nt]
+        flags = capi.KU_F_NO_COUNTS if cnt == "off" else 0
+        routed = rg.Routed(w)
+        try:
+            up = routed.upload(reads)
+            out.window(cell, lambda: routed.step(up, flags=flags))
+            rg.assert_step(routed, up, ref)
+            counts = routed.counts()
+            if cnt == "off":
+                rg.assert_zero_state(counts)
+            else:
+                rg.assert_counts(counts, ref)
+        finally:
+            routed.close()
+    except Exception:
+        out.fail(cell, traceback.format_exc(limit=6))
 
 
 def staged_cells(out, tmp):

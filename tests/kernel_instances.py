@@ -1,7 +1,8 @@
-"""Every gfx950 instance of the four classify kernel families, as data.
+"""Every gfx950 instance of the five classify kernel families, as data.
 
 `ku_classify_short_kernel<ITEMS, DO_COUNTS, KK, MM, WIN, OUT, ROUTE>` (ku_short.hip), `ku_lookup_kernel<MODE, LAYOUT, SHARDED,
-PRIOR, ITEMS>` (ku_kernels.hip), `ku_resolve_kernel<MODE>` (ku_kernels.hip) and `ku_seen_kernel<WHAT>` (ku_sparse.hip) are
+PRIOR, ITEMS>` (ku_kernels.hip), `ku_resolve_kernel<MODE>` (ku_kernels.hip), `ku_seen_kernel<WHAT>` (ku_sparse.hip) and
+`ku_route_owner_kernel<DO_COUNTS, KK, MM>` (ku_route.hip) are
 compiled once per template argument list, and the launchers pick one at run time.  A bug in one instance passes every test
 that launches its neighbours, so:
   - tests/test_kernel_instances.py (CPU) holds this table to the `.kd` symbols of the built library's gfx950 code objects;
@@ -22,7 +23,8 @@ Cell names: `<group>/<shape>/<output>/<counting>` for the fused kernel, where
   output  codes: ku_classify_batch; runs: ku_classify_batch_rle; sparse: ku_classify_batch_rle after ku_ctx_enable_sparse
           (OUT = 2 when counting); .../export and .../reset: ku_sparse_export and ku_ctx_reset_counts behind a sparse cell
   counting on, or off (KU_F_NO_COUNTS)
-and `quick/...` (KU_F_QUICK, min_hits 2), `route/...` (routed ku_mgpu_step_device on two ranks of device 0), `staged/...`
+and `quick/...` (KU_F_QUICK, min_hits 2), `route/...` (routed ku_mgpu_step_device on two ranks of device 0, k = 31, nt = 11),
+`route13/...` / `route15/...` (the same at nt = 13 / 15 over two narrow bin ranges, tests/route_geometry.py), `staged/...`
 (golden f1 / f8: sorted layout, shards of the bin range, two databases, ku_lookup_stats_device).
 """
 import fnmatch
@@ -51,7 +53,8 @@ def _matrix():
     cells["g13"] += ["p13/s128/codes/on", "p13/s128/runs/on", "p13/s128/sparse/on", "g13/w65535/codes/on",
                      "g13/w65536/codes/on", "g13/w65536/codes/off", "g13/quick/codes/on", "g13/quick/codes/off"]
     cells["g15"] += ["p15/s128/codes/on", "p15/s128/runs/on", "p15/s128/sparse/on", "p15/win/codes/on"]
-    cells["route"] = ["route/s128/codes/on", "route/s128/codes/off", "route/win/codes/on", "route/win/codes/off"]
+    cells["route"] = ["route/s128/codes/on", "route/s128/codes/off", "route/win/codes/on", "route/win/codes/off",
+                      "route13/s128/codes/on", "route13/s128/codes/off", "route15/s128/codes/on", "route15/s128/codes/off"]
     cells["staged"] = ["staged/sorted/codes/on", "staged/sorted/codes/off", "staged/shard/codes/on", "staged/shard/codes/off",
                        "staged/shard/resolve/on", "staged/prior/codes/on", "staged/prior/codes/off",
                        "staged/prior_sorted/codes/on", "staged/prior_sorted/codes/off", "staged/stats"]
@@ -137,8 +140,10 @@ ROWS = [
     (f"{_S}<2, false, 0, 0, true, 1, false>", "classify_batch_rle (sparse or not); any geometry; windowed; KU_F_NO_COUNTS",
      ("[gep]*/s193/runs/off", "[gep]*/win/runs/off", "[gep]*/s193/sparse/off", "[gep]*/win/sparse/off"), None),
     # ---- resolve stage of the owner-routed step (ROUTE): ku_mgpu_step_device, KU_MGPU_EXCHANGE=route
-    (f"{_S}<2, true, 0, 0, false, 0, true>", "routed step; longest <= 128 k-mers; counting", ("route/s128/codes/on",), None),
-    (f"{_S}<2, false, 0, 0, false, 0, true>", "routed step; <= 128; KU_F_NO_COUNTS", ("route/s128/codes/off",), None),
+    (f"{_S}<2, true, 0, 0, false, 0, true>", "routed step; longest <= 128 k-mers; counting",
+     ("route/s128/codes/on", "route1[35]/s128/codes/on"), None),
+    (f"{_S}<2, false, 0, 0, false, 0, true>", "routed step; <= 128; KU_F_NO_COUNTS",
+     ("route/s128/codes/off", "route1[35]/s128/codes/off"), None),
     (f"{_S}<2, true, 0, 0, true, 0, true>", "routed step; 129-65535 k-mers; counting", ("route/win/codes/on",), None),
     (f"{_S}<2, false, 0, 0, true, 0, true>", "routed step; 129-65535; KU_F_NO_COUNTS", ("route/win/codes/off",), None),
     (f"{_S}<2, true, 0, 0, false, 1, true>", "ku_launch_route_resolve with runs_out; <= 128; counting", (), _NOT_ROUTED_RUNS),
@@ -162,12 +167,20 @@ ROWS = [
     ("ku_lookup_kernel<0, 0, true, true, 1>", "second database, sorted layout, KU_F_NO_COUNTS",
      ("staged/prior_sorted/codes/off",), None),
     ("ku_lookup_kernel<2, 0, true, false, 1>", "ku_lookup_stats_device (bench.py's probe statistics)", ("staged/stats",), None),
-    ("ku_lookup_kernel<3, 1, true, false, 2>", "route scan of the routed step", ("route/*",), None),
+    ("ku_lookup_kernel<3, 1, true, false, 2>", "route scan of the routed step", ("route/*", "route1[35]/*"), None),
     # ---- staged resolve (MODE 0: <= 384 k-mers, 1: <= 12 288, 2: longer); the quick path has a kernel of its own
     ("ku_resolve_kernel<0>", "staged path, every read up to 384 k-mers",
      ("g13/w65536/codes/*", "staged/sorted/codes/*", "staged/shard/resolve/on", "staged/prior*/codes/*"), None),
     ("ku_resolve_kernel<1>", "staged path, reads of 385-12 288 k-mers", ("g13/w65536/codes/*",), None),
     ("ku_resolve_kernel<2>", "staged path, reads past 12 288 k-mers", ("g13/w65536/codes/*",), None),
+    # ---- the owner of the routed step (DO_COUNTS, KK, MM; 0, 0 = any other geometry)
+    ("ku_route_owner_kernel<true, 31, 13>", "routed step; k31 nt13; counting", ("route13/s128/codes/on",), None),
+    ("ku_route_owner_kernel<false, 31, 13>", "routed step; k31 nt13; KU_F_NO_COUNTS", ("route13/s128/codes/off",), None),
+    ("ku_route_owner_kernel<true, 31, 15>", "routed step; k31 nt15; counting", ("route15/s128/codes/on",), None),
+    ("ku_route_owner_kernel<false, 31, 15>", "routed step; k31 nt15; KU_F_NO_COUNTS", ("route15/s128/codes/off",), None),
+    ("ku_route_owner_kernel<true, 0, 0>", "routed step; any other geometry; counting", ("route/*/codes/on",), None),
+    ("ku_route_owner_kernel<false, 0, 0>", "routed step; other geometry; KU_F_NO_COUNTS (quick mode too: it counts in its resolve stage)",
+     ("route/*/codes/off",), None),
     # ---- SEEN marks of the probe table (sparse fast path)
     ("ku_seen_kernel<0>", "ku_sparse_export after an OUT = 2 batch: count the marks", ("*/sparse/on/export",), None),
     ("ku_seen_kernel<1>", "ku_sparse_export after an OUT = 2 batch: insert the marks into the run-wide set",
@@ -175,7 +188,7 @@ ROWS = [
     ("ku_seen_kernel<2>", "ku_ctx_reset_counts after an OUT = 2 batch: clear the marks", ("*/sparse/on/reset",), None),
 ]
 
-FAMILIES = ("ku_classify_short_kernel<", "ku_lookup_kernel<", "ku_resolve_kernel<", "ku_seen_kernel<")
+FAMILIES = ("ku_classify_short_kernel<", "ku_lookup_kernel<", "ku_resolve_kernel<", "ku_seen_kernel<", "ku_route_owner_kernel<")
 
 
 def all_cells():

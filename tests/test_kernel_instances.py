@@ -1,6 +1,6 @@
 """CPU: the instance table (tests/kernel_instances.py) equals what the compiler emitted.
 
-The `.kd` (kernel descriptor) symbols of the built library's gfx950 code objects name every kernel instance; the four classify
+The `.kd` (kernel descriptor) symbols of the built library's gfx950 code objects name every kernel instance; the five classify
 families among them must be exactly the table's rows.  An instance added to the source or removed from it fails here until
 its row exists (or is gone), so the GPU matrix cannot silently miss a new one.
 """
@@ -29,7 +29,7 @@ def _tool(name):
 
 
 def compiled_instances(lib, tmp):
-    """demangled names of the four families' kernels in the gfx950 code objects of `lib`"""
+    """demangled names of the five families' kernels in the gfx950 code objects of `lib`"""
     # llvm-objdump --offloading writes the extracted bundles next to its input: work on a copy
     copy = os.path.join(tmp, os.path.basename(lib))
     shutil.copyfile(lib, copy)
