@@ -181,6 +181,56 @@ int ku_db_merge_files(int device, const char *const *kdb_paths, const char *cons
                       const struct ku_tax *tax /* or NULL */, uint64_t device_bytes, const char *out_kdb_path,
                       const char *out_idx_path, ku_db_merge_stats *stats /* or NULL */);
 
+/* db_shrink on the GPU (src/db_shrink.cpp, which scripts/shrink_db.sh runs for krakenuniq-build --shrink and build_db.sh for
+ * --max-db-size): keeps n_out of the key_ct records of a Jellyfish-1 list, evenly spread, in the input's order.  The rule,
+ * with bs = key_ct / n_out and odd = key_ct % n_out: the records are cut into n_out consecutive blocks, the first odd of
+ * bs + 1 records and the others of bs, and of every block the record `offset` places before its end is kept
+ * (src/db_shrink.cpp:83-109), so output record j is input record
+ *   src(j) = (j + 1) * bs + min(j + 1, odd) - offset,
+ * and S(x) = #{ j : src(j) < x } output records come from the input records below x:
+ *   S(x) = min(odd, t / (bs + 1)) + (t >= odd ? clamp((t - odd) / bs - odd, 0, n_out - odd) : 0),   t = x + offset - 1.
+ *
+ * List mode (in_idx_path = out_idx_path = NULL): the input is any JFLISTDN file with 4-byte values, sorted or not, key_len
+ * 1..8; the output is the input's header with n_out at byte 48 and the selected records -- byte for byte the reference's file.
+ * Database mode (both index paths given): the input is a sorted database.kdb with its KRAKIX2 index.  The selection keeps
+ * the (minimizer bin key, k-mer) order, so the output is a sorted database as well, and its index follows from the old one
+ * without a bin key or a sort: new_offsets[b] = S(offsets[b]), closing offset n_out -- byte for byte what the reference's
+ * db_shrink followed by its db_sort -n nt writes (the two steps of scripts/shrink_db.sh), and what classify loads.
+ *
+ * On the device two kernels, both over ku_dbshrink_rule.h's arithmetic (64 bits throughout).  Select: the input travels in
+ * chunks of chunk_records consecutive records, [lo, hi), not aligned to the blocks; output record j of [S(lo), S(hi)) is copied
+ * from place src(j) - lo of the chunk to place j - S(lo) of a compact buffer that goes to the file (a chunk that selects
+ * nothing is not uploaded).  Offsets: the old index in slices of offset_slice entries, each mapped in place through S.
+ *   offset_slice = device_bytes / 8 / 8,   chunk_records = (device_bytes - device_bytes / 8) / 24
+ * (an eighth of the budget for the slice; per record of a chunk 12 bytes in its buffer and 12 in the buffer of the selected
+ * records, whatever key_len is).  device_bytes = 0: half of the HBM that is free; below KU_DBSHRINK_MIN_BYTES: KU_EINVAL.
+ * Every budget gives the same files.  The stages are synchronous.
+ *
+ * Checked before any device is touched and before any output is created: null kdb paths, only one of the two index paths,
+ * n_out or offset of 0, the budget (KU_EINVAL); an input that cannot be opened (KU_ENOINPUT); no JFLISTDN magic, val_len
+ * other than 4, key_bits odd, 0 or above 62, a file shorter than key_ct records, n_out > key_ct, offset > bs -- compared
+ * with bs also where blocks of bs + 1 records exist, as the reference does -- (KU_EDATA); an index that is not an index or
+ * not of the size its nt byte implies, or whose closing offset is not key_ct (KU_EDATA); a KRAKIDX index (KU_EINVAL: its
+ * bins are not those db_sort would make; the message names db_sort -n, which re-indexes a database); an output path that
+ * names the same file as an input or as the other output (device and inode compared; KU_EINVAL).  Then the device: KU_EHIP
+ * without one, KU_EINVAL "device index out of range".  A call that fails after it created the outputs removes them.
+ * Two deliberate differences from the reference: it never checks that the file holds key_ct records (and copies whatever its
+ * buffer held), and it leaves a header-only output behind when the offset is too large; here both are KU_EDATA with no
+ * output.  stats may be null. */
+#define KU_DBSHRINK_MIN_BYTES 65536
+typedef struct ku_db_shrink_stats {
+  uint64_t key_ct_in;     /* records of the input */
+  uint64_t key_ct_out;    /* records written: n_out */
+  uint64_t block_size;    /* bs */
+  uint64_t odd_blocks;    /* blocks of bs + 1 records */
+  uint64_t chunks;        /* chunks the input was cut into (those that select nothing included) */
+  uint64_t chunk_records; /* records per chunk under the budget */
+  double read_s, select_s, write_s; /* host clock around the (synchronous) stages: file to device; kernels; device to file */
+} ku_db_shrink_stats;
+int ku_db_shrink_files(int device, const char *in_kdb_path, const char *in_idx_path /* or NULL */, uint64_t n_out,
+                       uint64_t offset, uint64_t device_bytes, const char *out_kdb_path, const char *out_idx_path /* or NULL */,
+                       ku_db_shrink_stats *stats /* or NULL */);
+
 /* HyperLogLog sketches of a library's k-mers on the device: the reference's count_unique (src/count_unique.cpp, called by
  * scripts/build_db.sh:127 to size the Jellyfish hash), and the per-range estimates from which kmer_db -P auto plans its passes.
  *

@@ -95,6 +95,8 @@ SIGNATURES = {
     "ku_db_sort_files": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int]),
     "ku_db_merge_files": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_uint32, C.c_void_p, C.c_uint64,
                                     C.c_char_p, C.c_char_p, C.c_void_p]),
+    "ku_db_shrink_files": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p,
+                                     C.c_void_p]),
     "ku_kmerdb_open": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "ku_kmerdb_add": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64]),
     "ku_kmerdb_end_pass": (C.c_int, [C.c_void_p]),
@@ -976,6 +978,33 @@ def db_merge_files(kdb_paths, idx_paths, out_kdb, out_idx, tax=None, device_byte
     st = DbMergeStats()
     _chk(lib().ku_db_merge_files(device, kdbs, idxs, n, tax.h if tax is not None else None, device_bytes, os.fsencode(out_kdb),
                                  os.fsencode(out_idx), C.byref(st)), "ku_db_merge_files")
+    return st
+
+
+class DbShrinkStats(C.Structure):  # ku_db_shrink_stats
+    _fields_ = [(n, C.c_uint64) for n in ("key_ct_in", "key_ct_out", "block_size", "odd_blocks", "chunks", "chunk_records")] + \
+               [(n, C.c_double) for n in ("read_s", "select_s", "write_s")]
+
+
+KU_DBSHRINK_MIN_BYTES = 65536
+
+
+def db_shrink_capacity(device_bytes):
+    """the budget rule of ku_db_shrink_files: (records of an input chunk, offsets of an index slice).  One eighth of the budget
+    is the offset slice's at 8 bytes per offset, the rest the records' at 24 bytes each (12 in the chunk, 12 in the buffer of
+    the records selected from it)"""
+    offset_bytes = device_bytes // 8
+    return (device_bytes - offset_bytes) // 24, offset_bytes // 8
+
+
+def db_shrink_files(in_kdb, out_kdb, n_out, offset=1, in_idx=None, out_idx=None, device_bytes=0, device=0):
+    """db_shrink on the GPU (ku_db_shrink_files): n_out of the records of a Jellyfish-1 list, evenly spread, the one `offset`
+    places before the end of each block.  With in_idx and out_idx the input is a sorted database and its KRAKIX2 index, and the
+    output a sorted database with its index.  Returns the DbShrinkStats"""
+    st = DbShrinkStats()
+    enc = lambda p: os.fsencode(p) if p is not None else None
+    _chk(lib().ku_db_shrink_files(device, enc(in_kdb), enc(in_idx), n_out, offset, device_bytes, enc(out_kdb), enc(out_idx),
+                                  C.byref(st)), "ku_db_shrink_files")
     return st
 
 

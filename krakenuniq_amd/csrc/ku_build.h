@@ -1,5 +1,5 @@
 // ku_build.h -- host plumbing shared by the database build tools' translation units (ku_dbsort.hip, ku_kmerdb.hip, ku_dbmerge.hip,
-// ku_sketch.hip, ku_setlcas.hip): the device check, the KRAKIX2 scramble mask, the HIP check, launch geometry, rocPRIM's
+// ku_dbshrink.hip, ku_sketch.hip, ku_setlcas.hip): the device check, the KRAKIX2 scramble mask, the HIP check, launch geometry, rocPRIM's
 // two-call protocol and its grow-only scratch (KuScratch), the clock (ku_now), StreamGuard, the default device budget, the
 // staged copy from the device into the files of a KuDbFiles (ku_dbfiles.h: the one writer of a database.kdb + database.idx
 // pair), the taxonomy's node table (KuNodeTable), and what the other tools borrow from db_sort (dbsort_unpack,

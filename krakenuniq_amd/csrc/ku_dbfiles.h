@@ -1,5 +1,5 @@
-// ku_dbfiles.h -- the one writer of a database.kdb + database.idx pair (db_sort, kmer_db, db_merge; csrc/dbfiles_check.cpp
-// runs it without a device).  Plain C++ and POSIX, no HIP: the caller brings the bytes from wherever they are.
+// ku_dbfiles.h -- the one writer of a database.kdb + database.idx pair (db_sort, kmer_db, db_merge, db_shrink, which also
+// writes a list without an index; csrc/dbfiles_check.cpp runs it without a device).  Plain C++ and POSIX, no HIP: the caller brings the bytes from wherever they are.
 //   database.kdb  a Jellyfish-1 list header as KrakenDB reads it (krakendb.cpp:60-78,177; key_ct at byte 48), then the records
 //   database.idx  "KRAKIX2" or "KRAKIDX", the nt byte, then 4^nt + 1 offsets (make_index, krakendb.cpp:118-148)
 // Files of a run that did not reach the end of finish() are not databases: none is left behind.
@@ -40,6 +40,7 @@ struct KuDbFiles {
   int kdb_fd = -1, idx_fd = -1;
   bool made_kdb = false, made_idx = false;  // created here, and not yet a finished database
   bool bad = false;
+  bool with_idx = true;  // false: a list without an index
 
   KuDbFiles() = default;
   KuDbFiles(const KuDbFiles &) = delete;
@@ -56,9 +57,18 @@ struct KuDbFiles {
     if (!made_idx) return failed("can't write " + idx_path);
     return true;
   }
+  // a list without an index (db_shrink's list mode): creates and truncates the .kdb alone; begin() and finish() then leave
+  // the index out, and append_offsets() fails
+  bool open(const std::string &kdb) {
+    kdb_path = kdb;
+    with_idx = false;
+    made_kdb = (kdb_fd = ::open(kdb.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) >= 0;
+    return made_kdb || failed("can't write " + kdb_path);
+  }
   // the database header as handed in; the index's magic (idx_type 1: KRAKIDX, else KRAKIX2) and its nt byte
   bool begin(const void *kdb_header, size_t n, uint32_t idx_type, uint32_t nt) {
     const uint8_t nt8 = (uint8_t)nt;
+    if (!with_idx) return put(kdb_fd, kdb_path, kdb_header, n);
     return put(kdb_fd, kdb_path, kdb_header, n) && put(idx_fd, idx_path, idx_type == 1 ? "KRAKIDX" : "KRAKIX2", 7) &&
            put(idx_fd, idx_path, &nt8, 1);
   }
@@ -67,7 +77,7 @@ struct KuDbFiles {
   // offsets[4^nt] = key_ct (make_index, krakendb.cpp:136-139); key_ct into the header (krakendb.cpp:72); both files closed.
   // True: every step of the run succeeded, and the files stay.
   bool finish(uint64_t key_ct) {
-    put(idx_fd, idx_path, &key_ct, 8);
+    if (with_idx) put(idx_fd, idx_path, &key_ct, 8);
     if (!bad && ::pwrite(kdb_fd, &key_ct, 8, 48) != 8) failed("write error on " + kdb_path);
     if (!bad && close_fd(idx_fd) != 0) failed("write error on " + idx_path);
     if (!bad && close_fd(kdb_fd) != 0) failed("write error on " + kdb_path);

@@ -1,6 +1,6 @@
 // ku_kmerdb.h -- device helpers of the k-mer set builder (ku_kmerdb_*, bin/kmer_db; entry points and the extraction
 // kernel in ku_kmerdb.hip) and of the other build tools: the minimizer bin key (db_sort's second half, set_lcas), the on-disk
-// record codec (db_sort, db_merge), the taxid -> node lookup (set_lcas, db_merge), and the tile decoding that turns sequence
+// record codec (db_sort, db_merge, db_shrink), the taxid -> node lookup (set_lcas, db_merge), and the tile decoding that turns sequence
 // bytes into k-mers, shared with the sketch kernel (ku_sketch.hip).  Helpers, constants and argument structs only: a kernel
 // lives in the one .hip file that launches it.
 #pragma once

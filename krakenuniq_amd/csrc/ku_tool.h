@@ -1,4 +1,4 @@
-// ku_tool.h -- what the database build programs share (db_sort, set_lcas, kmer_db, count_unique, db_merge): the fatal exit of the
+// ku_tool.h -- what the database build programs share (db_sort, set_lcas, kmer_db, count_unique, db_merge, db_shrink): the fatal exit of the
 // program and of its input stage, the exit code of a library status, the device to use, the size that -s takes, the list of input
 // files, and the loop over their FASTA records.  Plain C++ over the C ABI, no HIP.
 #pragma once
