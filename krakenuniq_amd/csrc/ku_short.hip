@@ -104,7 +104,7 @@ __device__ __forceinline__ void ks_ct_flush(uint32_t *key, uint32_t *cnt, uint32
 #ifdef KS_DIAG_NOHOT  // (diagnostic builds: is it the ONE address every wave adds to -- the misses' counter -- that the flushes cost?)
     if (kk == 1) kk = 0;
 #endif
-    if (hot && kk == 1) { *hot = cnt[i]; kk = 0; }
+    if (hot && kk == 1) { *hot += cnt[i]; kk = 0; }  // (one lane holds the key; the word was zeroed in front of the call, the end of the kernel: a second hot flush adds)
     if (kk) atomicAdd(&global[kk - 1], (unsigned long long)cnt[i]);
     key[i] = 0;
     cnt[i] = 0;
@@ -148,7 +148,7 @@ __device__ __forceinline__ void ks_rct_flush(uint32_t *key, uint32_t *cnt, uint3
 #ifdef KS_DIAG_NOHOT
     if (kk - 1 == KS_RCT_SLOT) kk = 0;  // (the unclassified reads' counter)
 #endif
-    if (hot && kk - 1 == KS_RCT_SLOT) { *hot = cnt[i]; kk = 0; }  // (reads without a hit: node 0, see ks_ct_flush)
+    if (hot && kk - 1 == KS_RCT_SLOT) { *hot += cnt[i]; kk = 0; }  // (reads without a hit: node 0, see ks_ct_flush)
     if (kk) atomicAdd(&global[ks_rct_node(kk - 1, tax)], (unsigned long long)cnt[i]);
     key[i] = 0;
     cnt[i] = 0;
@@ -421,7 +421,12 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
   // 1 skip probe, 2 skip HLL, 4 skip n_kmers, 8 skip taxa store,
   // 32 skip resolve (call 0), 64 skip locus/minimizer stage (bucket 0), 128 (OUT = 2) skip the SEEN marks, 256 (OUT = 2) skip
   // the misses' inserts into the run-wide set, 512 (OUT = 2) skip the insert counts per (unit, slot), 1024 skip the probe's
-  // straggler pass (a lookup that the first entry compare leaves open stays a miss: wrong for spilled k-mers).  0 in production.
+  // straggler pass (a lookup that the first entry compare leaves open stays a miss: wrong for spilled k-mers), 2048 no text
+  // round trip (T1) behind a wave's first read: every later read decodes the first one's two dwords again (wrong results), 4096 no
+  // round trip behind the probe (T4) of a single-taxon read: its code is the slot, both HLL floors are 0.  (Neither of the two bounds
+  // a gain: both change what the HLL filter lets through and run SLOWER than the whole kernel)  0 in production.
+  // NO wave may leave this function early (no `return` in or before the read loop): the hot-counter epilogue at the end of the kernel
+  // has the kernel's one __syncthreads(), and a block whose waves do not all arrive there hangs.
   using G = KsGeom<ITEMS>;
   constexpr uint32_t TCAP = 1u << G::TCAP_LOG2;
   using Lds = KsWaveLds<ITEMS, WIN, !ROUTE, DO_COUNTS && !ROUTE>;
@@ -509,6 +514,35 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     const uint64_t r0 = (uint64_t)blockIdx.x * KS_WAVES + wv;
     if (ks_less64(r0, n_reads)) { len_n = seq_len[r0]; off_n = seq_off[r0]; }
   }
+  // The read's text, one read ahead (one-pass instances whose stage 1 is one round of lanes).  A wave's vector loads complete in issue
+  // order and a wait leaves the youngest ones outstanding: the next read's two dwords per lane, requested BEHIND the last loads this
+  // read waits for (the single taxon's code and floors; the several-taxa read's gathers), cost none of this read's waits anything and
+  // are on their way during the accounting, the output stores and the loop edge -- where they were requested at the top of the read
+  // and waited for at once.  They live in two registers from there to stage 1 only: the scan's and the probe's registers are dead by
+  // then (requested at the top of the read before, they were held across the register peak for nothing gained).  There is ONE
+  // request per read and no branch around it: where two paths meet, the compiler's wait covers the one on which the awaited load is
+  // the younger, and a second request site gives the text two homes, i.e. a copy that waits for it.  So a several-taxa read
+  // issues its own gathers (floors, taxids, the call's taxid) in front of it too, and a next read that is none, has no k-mer or ends
+  // on the buffer's last bytes aims the request at seq_off[0]; stage 1 decides by the same scalar test.
+  constexpr uint32_t S1_LANES = ROUTE ? 0u : (uint32_t)((G::NWORDS * 4 + 63) / 64) * 64;
+  // (not the sparse emulation's instances, OUT = 2: they sit at 80 registers through the accounting too, and the two more spill)
+  constexpr bool AHEAD = !WIN && !ROUTE && S1_LANES == 64 && OUT != 2;
+  uint32_t tx0 = 0, tx1 = 0;
+#ifdef KU_ABLATION
+  uint32_t tf0 = 0, tf1 = 0;  // (bit 2048: the dwords of the wave's first read)
+#endif
+  // `first`: the request in front of the loop, for the wave's first read (measurement bit 2048 leaves that one alone and sends
+  // every later one to the dummy address)
+  auto text_request = [&](bool first) {
+    const bool want = len_n >= k && ks_less64(off_n + len_n + 6, n_bytes);
+    const uint32_t *tq = reinterpret_cast<const uint32_t *>(seqs + (off_n & ~3ull)) + (min(4 * lane, (len_n - 1u) & ~3u) >> 2);
+    // the dummy address: the 8 bytes of seq_off[0] as two dwords.  They exist because the launch has a read: the launcher returns
+    // before the launch when n_reads == 0 (ku_launch_classify_short), and ROUTE instances, whose `seqs` is null, never come here
+    if (!want || (KS_ABL(2048u) && !first)) tq = reinterpret_cast<const uint32_t *>(seq_off);
+    tx0 = tq[0];
+    tx1 = tq[1];
+  };
+  if (AHEAD) text_request(true);
   for (uint64_t r = (uint64_t)blockIdx.x * KS_WAVES + wv; ks_less64(r, n_reads); r += n_waves) {
     // length and offset were requested one read ahead (two scalar loads off the chain of dependent round trips)
     const uint32_t rlen = len_n;
@@ -572,7 +606,6 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
       // cover any four of its bytes lie inside the buffer" is false for the last read(s) of a batch only; everywhere else a
       // lane fetches its two dwords from the read's aligned base + 4 * lane with no test of its own, and the byte alignment is the
       // read's, not the lane's.  Lanes behind the read's end fetch its last dword again and mark every base ambiguous.
-      constexpr uint32_t S1_LANES = (uint32_t)((G::NWORDS * 4 + 63) / 64) * 64;
       // the stores below come from every lane: the four lanes of a quad hold the same word, and a word index behind NWORDS either
       // still lies inside the arrays (ITEMS = 2) or is clamped to their last element; nothing reads a word behind NWORDS for a
       // position that belongs to the read
@@ -587,8 +620,19 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
         const uint32_t valid = len - min(b0, len);  // bases of this dword that belong to the read
         uint32_t c8 = 0, a4 = 0xFu;
         if (text_inside) {
-          const uint32_t *q = text + (min(b0, last_dw) >> 2);  // two aligned dwords cover the four bytes at any alignment
-          ku_pack_dword(__builtin_amdgcn_alignbyte(q[1], q[0], text_sh), c8, a4);
+          uint32_t d0 = tx0, d1 = tx1;  // (AHEAD: requested inside the read before, by this very test)
+#ifdef KU_ABLATION
+          if (AHEAD && KS_ABL(2048u)) {
+            if (ks_less64(r, n_waves)) { tf0 = d0; tf1 = d1; }
+            else { d0 = tf0; d1 = tf1; }
+          }
+#endif
+          if (!AHEAD) {
+            const uint32_t *q = text + (min(b0, last_dw) >> 2);  // two aligned dwords cover the four bytes at any alignment
+            d0 = q[0];
+            d1 = q[1];
+          }
+          ku_pack_dword(__builtin_amdgcn_alignbyte(d1, d0, text_sh), c8, a4);
         } else if (b0 < len) {
           const uint64_t a = off + b0;
           uint32_t d = 0;
@@ -937,24 +981,39 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     }
 
     // the taxid of the single taxon is requested here: its round trip runs under the HLL loads below
-    const uint32_t uni_code = uni && uni_slot ? tax.slot_taxid[uni_slot] : 0u;
+    // (AHEAD: a several-taxa read's call comes through the same register, below)
+    uint32_t uni_code = KS_ABL(4096u) ? uni_slot : (uni && uni_slot ? tax.slot_taxid[uni_slot] : 0u);
     // so are the two HLL floors such a read needs, the misses' and the taxon's (past this CU's L1, which another CU's raise of
     // a floor never reaches)
     const bool fl_on = DO_COUNTS && !ROUTE && floor_every != 0 && n > 0;
     uint32_t fl_miss = 0, fl_hit = 0;
-    if (fl_on && uni) {
-      fl_miss = ks_gload(&cnt.hll_floor[0]);
-      fl_hit = ks_gload(&cnt.hll_floor[uni_slot]);
+    uint32_t fl[ITEMS], tcode[ITEMS];  // floor and taxid per k-mer (slot 0, a miss: taxid 0)
+    if (uni) {
+      if (fl_on && !KS_ABL(4096u)) {
+        fl_miss = ks_gload(&cnt.hll_floor[0]);
+        fl_hit = ks_gload(&cnt.hll_floor[uni_slot]);
+      }
+    } else if (AHEAD) {  // several taxa: everything the lanes gather by slot, and the call's taxid, all in front of the text
+      if (fl_on) {
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) fl[j] = ks_gload(&cnt.hll_floor[v[j]]);
+      }
+#pragma unroll
+      for (int j = 0; j < ITEMS; ++j) tcode[j] = tax.slot_taxid[v[j]];
+      uni_code = tax.node_taxid[call_node];
     }
+    if (AHEAD) text_request(false);  // the next read's text, behind the last loads this read waits for
 
     // ---- ReadCounts::add_kmer for every unambiguous k-mer, misses included (classify.cpp:939): HLL register per
     // k-mer; n_kmers per read when the read met one taxon at most (two counter updates instead of one per lane)
     uint32_t n_hit = 0, n_miss = 0;
     if (DO_COUNTS && !ROUTE && n > 0) {
-      uint32_t rank[ITEMS], fl[ITEMS];
-      if (fl_on && !uni) {  // several taxa: each lane fetches the floors of its own slots
+      uint32_t rank[ITEMS];
+      if (fl_on && !uni) {  // several taxa: each lane fetches the floors of its own slots (AHEAD: it has, above)
+        if (!AHEAD) {
 #pragma unroll
-        for (int j = 0; j < ITEMS; ++j) fl[j] = ks_gload(&cnt.hll_floor[v[j]]);
+          for (int j = 0; j < ITEMS; ++j) fl[j] = ks_gload(&cnt.hll_floor[v[j]]);
+        }
       } else {
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) fl[j] = v[j] ? fl_hit : fl_miss;
@@ -1065,11 +1124,11 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     }
 
     // ---- outputs
-    uint32_t tcode[ITEMS];  // taxid per k-mer: slot 0 (miss) is taxid 0; the lookups of all items go out together
+    // taxid per k-mer; the lookups of all items go out together (AHEAD: they have, in front of the text request)
     if (uni) {
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) tcode[j] = v[j] ? uni_code : 0u;
-    } else {
+    } else if (!AHEAD) {
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) tcode[j] = tax.slot_taxid[v[j]];
     }
@@ -1119,7 +1178,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
         ro.run_cnt[r] = run_n;
       }
       if (lane == 0) {
-        calls[r] = uni ? uni_code : tax.node_taxid[call_node];
+        calls[r] = uni || AHEAD ? uni_code : tax.node_taxid[call_node];
         // incrementReadCount (classify.cpp:968): per node; single-taxon reads are booked under their slot and become
         // nodes when the wave's table is flushed
         if (DO_COUNTS) ks_rct_add<G::RCT_LOG2>(sw.rk, sw.rc, &misc[1], uni ? (KS_RCT_SLOT | uni_slot) : call_node, tax, cnt.n_reads);
@@ -1182,7 +1241,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     // the counters every wave holds -- misses (slot 0), reads without a hit (node 0) -- leave the block as ONE add each
     // (in misc[2] and [3]: the resolve list and the windowed table are done with)
     ks_wave_sync();
-    if (lane < 2) misc[2 + lane] = 0;
+    if (lane < 2) misc[2 + lane] = 0;  // (the hot flushes below ADD into these two words)
     if (!ROUTE && hq_fill) ks_hq_drain(hq, hq_fill, cnt.registers, lane);
     if (!ROUTE && fl_scan) ks_floor_scan(cnt.registers, cnt.hll_floor, fl_scan - 1u, lane);
     if (!ROUTE) ks_ct_flush<G::KCT_LOG2>(sw.kk, sw.kc, &misc[0], cnt.n_kmers, lane, &misc[2]);
