@@ -346,6 +346,8 @@ extern "C" int ku_ctx_create(int device, ku_ctx **out) {
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   HIP_TRY(hipMalloc((void **)&ctx->d_scalar, 128));
+  HIP_TRY(hipMalloc((void **)&ctx->claim.d, KU_CLAIM_CELLS * 8));
+  HIP_TRY(hipMemset(ctx->claim.d, 0, KU_CLAIM_CELLS * 8));
   if (const char *e = getenv("KU_LAYOUT")) ctx->hash_layout = strcmp(e, "sorted") != 0;
   if (const char *e = getenv("KU_LOAD_FACTOR")) {
     double f = atof(e);
@@ -439,6 +441,7 @@ extern "C" void ku_ctx_destroy(ku_ctx *ctx) {
                     &ctx->b_roff, &ctx->b_rcnt})
     b->release();
   if (ctx->d_scalar) (void)hipFree(ctx->d_scalar);
+  if (ctx->claim.d) (void)hipFree(ctx->claim.d);
   if (ctx->pf.d_scalar) (void)hipFree(ctx->pf.d_scalar);
   if (ctx->pf.stream) (void)hipStreamDestroy(ctx->pf.stream);
   for (RleJob &j : ctx->rle) j.release();

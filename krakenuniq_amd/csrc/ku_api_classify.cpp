@@ -174,7 +174,7 @@ int classify_device_impl(ku_ctx *ctx, const void *d_seqs, uint64_t n_bytes, cons
     }
     if (fused) {
       int st = ku_launch_classify_short(ctx->m.db, ctx->tax, ctx->cnt, (const uint8_t *)d_seqs, n_bytes, d_seq_off, d_seq_len,
-                                        n_reads, max_n, flags, d_calls, d_taxa, d_hits, ctx->b_ws.p, ctx->b_ws.cap, ctx->n_cu, s);
+                                        n_reads, max_n, flags, d_calls, d_taxa, d_hits, ctx->b_ws.p, ctx->b_ws.cap, ctx->n_cu, s, ctx->claim);
       return st == KU_OK ? KU_OK : fail(st, "fused short-read kernel launch failed");
     }
     ku_opts o = opts ? *opts : ku_opts{0, 1, 0, 0};

@@ -266,7 +266,8 @@ struct RlePlan {
   uint64_t n_seg() const { return seg.size() - 1; }
 };
 // seq_off: the reads' offsets when the batch may go up in segments (they ascend), else null: one segment.  test_hook: KU_RUNS_CAP applies.
-static RlePlan rle_plan(const ku_ctx *ctx, uint64_t n_bytes, uint64_t n_reads, uint32_t max_n, const uint64_t *seq_off, bool test_hook) {
+// flags: the batch's (KU_F_NO_COUNTS selects other kernel instances, whose grids may differ).
+static RlePlan rle_plan(const ku_ctx *ctx, uint64_t n_bytes, uint64_t n_reads, uint32_t max_n, uint32_t flags, const uint64_t *seq_off, bool test_hook) {
   RlePlan p;
   // ---- segments of the batch: cut at read boundaries, uploaded one after the other on the copy stream while the
   // compute stream classifies the ones before
@@ -283,7 +284,7 @@ static RlePlan rle_plan(const ku_ctx *ctx, uint64_t n_bytes, uint64_t n_reads, u
   p.seg[n_seg] = n_reads;
   uint64_t max_seg_reads = 0;
   for (uint64_t g = 0; g < n_seg; ++g) {
-    p.total_waves += ku_short_grid_waves(p.seg[g + 1] - p.seg[g], max_n, ctx->n_cu);
+    p.total_waves += ku_short_grid_waves(p.seg[g + 1] - p.seg[g], max_n, ctx->n_cu, !(flags & KU_F_NO_COUNTS));
     max_seg_reads = std::max(max_seg_reads, p.seg[g + 1] - p.seg[g]);
   }
   // a wave claims `chunk` run entries at a time: large enough for few claims, small enough that the unused tails of the
@@ -298,6 +299,15 @@ static RlePlan rle_plan(const ku_ctx *ctx, uint64_t n_bytes, uint64_t n_reads, u
   return p;
 }
 
+// sizes that hold a batch whatever its flags (callers that size buffers ahead of the batches)
+static RlePlan rle_plan_any_flags(const ku_ctx *ctx, uint64_t n_bytes, uint64_t n_reads, uint32_t max_n) {
+  RlePlan p = rle_plan(ctx, n_bytes, n_reads, max_n, 0, nullptr, false);
+  const RlePlan q = rle_plan(ctx, n_bytes, n_reads, max_n, KU_F_NO_COUNTS, nullptr, false);
+  p.runs_cap = std::max(p.runs_cap, q.runs_cap);
+  p.ws = std::max(p.ws, q.ws);
+  return p;
+}
+
 // no batch may be in flight (entry points that read or change what the batches in flight work on)
 int rle_idle(const ku_ctx *ctx, const char *who) {
   if (ctx->rle_in_flight) return fail(KU_ESTATE, std::string(who) + ": batches are in flight (ku_classify_batch_rle_finish first)");
@@ -306,7 +316,7 @@ int rle_idle(const ku_ctx *ctx, const char *who) {
 
 extern "C" uint64_t ku_device_rle_runs_cap(const ku_ctx *ctx, uint64_t n_bytes, uint64_t n_reads, uint32_t max_read_len) {
   if (!ctx || !ctx->tax_set) return 0;
-  return rle_plan(ctx, n_bytes, n_reads, ku_max_kmers(ctx->m.db.k, max_read_len), nullptr, false).runs_cap;
+  return rle_plan_any_flags(ctx, n_bytes, n_reads, ku_max_kmers(ctx->m.db.k, max_read_len)).runs_cap;
 }
 
 extern "C" int ku_classify_batch_device_rle(ku_ctx *ctx, const void *d_seqs, uint64_t n_bytes, const uint64_t *d_seq_off,
@@ -327,7 +337,7 @@ extern "C" int ku_classify_batch_device_rle(ku_ctx *ctx, const void *d_seqs, uin
     return fail(KU_EUNSUP, "the sparse-mode emulation runs through the host-buffer entry points (it needs the read lengths on the host)");
   if (!store_whole(ctx->m) || !rle_fused_eligible(ctx, o.flags, max_n, n_bytes, n_reads, true))
     return fail(KU_EUNSUP, "ku_classify_batch_device_rle: the fused kernel does not apply to this context / these options (ku_classify_batch_device does)");
-  const RlePlan p = rle_plan(ctx, n_bytes, n_reads, max_n, nullptr, false);  // (the caller's run array: its own runs_cap)
+  const RlePlan p = rle_plan(ctx, n_bytes, n_reads, max_n, o.flags, nullptr, false);  // (the caller's run array: its own runs_cap)
   if (p.ws > ctx->b_ws.cap) HIP_TRY(hipStreamSynchronize(s));
   if (ctx->b_ws.reserve(p.ws)) return fail(KU_ENOMEM, "device memory for the windowed kernel's workspace");
   KuRunsOut ro{};
@@ -343,7 +353,7 @@ extern "C" int ku_classify_batch_device_rle(ku_ctx *ctx, const void *d_seqs, uin
     ro.pre_base1 = 1;
   }
   int st = ku_launch_classify_short(ctx->m.db, ctx->tax, ctx->cnt, (const uint8_t *)d_seqs, n_bytes, d_seq_off, d_seq_len, n_reads, max_n, o.flags,
-                                    d_calls, nullptr, nullptr, ctx->b_ws.p, ctx->b_ws.cap, ctx->n_cu, s, &ro, nullptr);
+                                    d_calls, nullptr, nullptr, ctx->b_ws.p, ctx->b_ws.cap, ctx->n_cu, s, ctx->claim, &ro, nullptr);
   return st == KU_OK ? KU_OK : fail(st, "fused kernel launch failed");
 }
 
@@ -447,7 +457,7 @@ static int queue_uploads_and_launches(ku_ctx *ctx, RleJob &j, const RleBatch &b,
     ro.run_off = (uint64_t *)j.roff.p + a;
     ro.run_cnt = (uint32_t *)j.rcnt.p + a;
     ro.pre_base1 = (uint32_t)(1 + waves_before);
-    waves_before += ku_short_grid_waves(e - a, b.max_n, ctx->n_cu);
+    waves_before += ku_short_grid_waves(e - a, b.max_n, ctx->n_cu, !(b.o.flags & KU_F_NO_COUNTS));
     if (sparse) sf->unit_of = (const uint32_t *)j.unit.p + a;
     if (RleTimes::on && !*clock_started) {  // (behind the first segment's upload)
       if (!RleTimes::ref) { KU_TRY(ensure_event(RleTimes::ref, hipEventDefault)); HIP_TRY(hipEventRecord(RleTimes::ref, s)); }
@@ -456,7 +466,7 @@ static int queue_uploads_and_launches(ku_ctx *ctx, RleJob &j, const RleBatch &b,
     }
     int st = ku_launch_classify_short(ctx->m.db, ctx->tax, ctx->cnt, (const uint8_t *)j.seqs.p, b.n_bytes, (const uint64_t *)j.off.p + a,
                                       (const uint32_t *)j.len.p + a, e - a, b.max_n, b.o.flags, (uint32_t *)j.calls.p + a, nullptr, nullptr,
-                                      j.ws.p, j.ws.cap, ctx->n_cu, s, &ro, sf);
+                                      j.ws.p, j.ws.cap, ctx->n_cu, s, ctx->claim, &ro, sf);
     if (st != KU_OK) { (void)hipStreamSynchronize(ctx->h2d_stream); (void)hipStreamSynchronize(s); return fail(st, "fused kernel launch failed"); }
   }
   return KU_OK;
@@ -541,7 +551,7 @@ static int rle_job_enqueue(ku_ctx *ctx, RleJob &j, const RleBatch &b) {
   KuSparseFast sf{};
   {
     RleTimes::Lap lap{g_rle.t[5]};
-    p = rle_plan(ctx, b.n_bytes, b.n_reads, b.max_n, b.monotonic ? b.seq_off : nullptr, /*test_hook=*/true);
+    p = rle_plan(ctx, b.n_bytes, b.n_reads, b.max_n, b.o.flags, b.monotonic ? b.seq_off : nullptr, /*test_hook=*/true);
     // (the work units come before the buffers: their number sizes the counters)
     KU_TRY(plan_work_units(ctx, j, b, sparse));
     // (the job's buffers are its own and its previous batch is through: growing them needs no synchronisation of ours)
@@ -601,7 +611,7 @@ static int rle_job_finish(ku_ctx *ctx, RleJob &j, uint64_t *n_runs, bool *classi
     if (ctx->b_ws.reserve(rle_workspace_bytes(ctx, j.b.max_n, j.b.n_reads))) return fail(KU_ENOMEM, "device batch buffers");
     int st = ku_launch_classify_short(ctx->m.db, ctx->tax, ctx->cnt, (const uint8_t *)j.seqs.p, j.b.n_bytes, (const uint64_t *)j.off.p,
                                       (const uint32_t *)j.len.p, j.b.n_reads, j.b.max_n, j.b.o.flags | KU_F_NO_COUNTS, (uint32_t *)ctx->b_calls.p,
-                                      (uint32_t *)ctx->b_taxa.p, nullptr, ctx->b_ws.p, ctx->b_ws.cap, ctx->n_cu, s);
+                                      (uint32_t *)ctx->b_taxa.p, nullptr, ctx->b_ws.p, ctx->b_ws.cap, ctx->n_cu, s, ctx->claim);
     if (st != KU_OK) return fail(st, "fused kernel launch failed");
     KU_TRY(rle_and_fetch(ctx, (const uint32_t *)ctx->b_taxa.p, (const uint64_t *)j.off.p, (const uint32_t *)j.len.p, j.b.n_reads, j.b.n_bytes + 1,
                          false, j.b.calls, nullptr, j.b.run_off, j.b.run_cnt, n_runs));
@@ -771,7 +781,7 @@ extern "C" int ku_classify_batch_rle_reserve(ku_ctx *ctx, uint64_t n_bytes, uint
   KU_TRY(ensure_stream(ctx->h2d_stream));
   KU_TRY(ensure_stream(ctx->d2h_stream));
   KU_TRY(ensure_stream(ctx->fetch_stream));
-  const RlePlan p = rle_plan(ctx, n_bytes, n_reads, ku_max_kmers(ctx->m.db.k, max_read_len), nullptr, false);
+  const RlePlan p = rle_plan_any_flags(ctx, n_bytes, n_reads, ku_max_kmers(ctx->m.db.k, max_read_len));
   const bool sparse = ctx->sp.on && ctx->sp.unit_nt;
   const uint64_t n_units = sparse ? n_bytes / ctx->sp.unit_nt + 2 : 0;
   for (uint32_t q = 0; q < std::min<uint32_t>(n_jobs, KU_RLE_MAX_IN_FLIGHT); ++q)

@@ -222,6 +222,7 @@ struct ku_ctx {
   hipEvent_t main_ev = nullptr;
   hipEvent_t prev_kernels_done = nullptr;  // (a job's event, not owned)
   uint32_t *d_scalar = nullptr;
+  KuClaimCells claim;  // the fused kernel's claim counters, one cell per stream it is launched on (ku_internal.h)
   // ku_classify_batch_rle in two steps: up to KU_RLE_MAX_IN_FLIGHT batches in flight (FIFO: rle_head is the oldest)
   RleJob rle[KU_RLE_MAX_IN_FLIGHT];
   int rle_head = 0, rle_in_flight = 0;

@@ -262,6 +262,30 @@ struct KuRouteIn {
   const uint32_t *ret;  // the slots the owners returned, in that numbering
 };
 #define KU_SPARSE_SWITCH_INSERTS 1025u  // fewest inserts with which a sparse sketch can turn dense (hyperloglogplus.cpp:496-498)
+// The fused kernel's claim counters (ku_short.hip: the waves of a launch take their reads `chunk` at a time from one counter of the
+// launch).  A cell is two words, {next, done}: reads claimed so far, and waves that are through; the launch's last wave sets both
+// back to 0, so a launch costs no memset and no kernel beside its own.  Two launches that may run at the same time must not
+// share a cell, and the host cannot tell when a launch is over without waiting for it.  What it can tell is the stream: the launches
+// of one stream run one after the other, and a kernel's last stores are done before the next kernel of its stream starts.  So the
+// ring's cells are taken in turn BY STREAM -- a stream keeps the cell of its first launch -- and no count of launches in flight
+// enters: the library itself launches the fused kernel on three streams of a context (its own, and the two the host-batch call's
+// batches take turns on, ku_ctx::k_streams; KU_RLE_MAX_IN_FLIGHT batches of up to 8 segments queue on those two), the rest of
+// the ring is for the streams callers hand to the device entry points.  A launch on one stream more than the ring has cells would
+// have to take a cell that may be live: it is refused (KU_EINVAL).
+#define KU_CLAIM_CELLS 32
+struct KuClaimCells {
+  uint32_t *d = nullptr;  // KU_CLAIM_CELLS x {next, done} on the device, all 0 between launches
+  hipStream_t owner[KU_CLAIM_CELLS] = {};
+  int n_bound = 0;
+  // the cell of `stream`'s launches (null: the ring is bound to KU_CLAIM_CELLS other streams)
+  uint32_t *cell(hipStream_t stream) {
+    for (int i = 0; i < n_bound; ++i)
+      if (owner[i] == stream) return d + 2 * i;
+    if (!d || n_bound == KU_CLAIM_CELLS) return nullptr;
+    owner[n_bound] = stream;
+    return d + 2 * n_bound++;
+  }
+};
 // fused wave-per-read path for short reads (ku_short.hip)
 uint32_t ku_short_max_kmers(const KuDbDev &db);           // reads taken in one pass
 uint32_t ku_short_max_kmers_windowed(const KuDbDev &db);  // ... in windows of 128 k-mers (ku_short.hip)
@@ -269,7 +293,7 @@ uint64_t ku_short_workspace_bytes(uint32_t max_kmers, uint32_t n_slots, uint64_t
 int ku_launch_classify_short(const KuDbDev &db, const KuTaxDev &tax, const KuCountsDev &cnt, const uint8_t *d_seqs,
                              uint64_t n_bytes, const uint64_t *d_seq_off, const uint32_t *d_seq_len, uint64_t n_reads,
                              uint32_t max_kmers, uint32_t flags, uint32_t *d_calls, uint32_t *d_taxa, uint32_t *d_hits,
-                             void *d_workspace, uint64_t workspace_bytes, int n_cu, hipStream_t stream,
+                             void *d_workspace, uint64_t workspace_bytes, int n_cu, hipStream_t stream, KuClaimCells &cells,
                              const KuRunsOut *runs_out = nullptr, const KuSparseFast *sparse = nullptr);
 // resolve stage of the owner-routed path fused with the gather of the returned slots (ku_short.hip, ROUTE instances)
 uint32_t ku_route_resolve_max_kmers();
@@ -278,8 +302,9 @@ int ku_launch_route_resolve(const KuDbDev &db, const KuTaxDev &tax, const KuCoun
                             uint32_t *d_taxa, uint32_t *d_hits, const uint32_t *d_kb, const uint32_t *d_ret, void *d_workspace,
                             uint64_t workspace_bytes, int n_cu, hipStream_t stream, const KuRunsOut *runs_out = nullptr);
 // waves of the fused kernel's persistent grid for a batch of n_reads (sizing of the run array: every wave may leave one
-// partly used chunk behind)
-uint64_t ku_short_grid_waves(uint64_t n_reads, uint32_t max_kmers, int n_cu);
+// partly used chunk behind); counts: the launch is not KU_F_NO_COUNTS (the instance decides whether the waves claim their reads, and
+// with that the grid: ku_short.hip, ks_claim_instance)
+uint64_t ku_short_grid_waves(uint64_t n_reads, uint32_t max_kmers, int n_cu, bool counts);
 uint64_t ku_resolve_workspace_bytes(uint32_t max_read_len, uint32_t k, int n_cu);
 int ku_launch_exact(uint32_t k, const uint8_t *d_seqs, const uint64_t *d_seq_off, const uint32_t *d_seq_len, uint64_t n_reads,
                     const uint32_t *d_taxa, unsigned long long *d_set, uint64_t mask, unsigned long long *d_unique,

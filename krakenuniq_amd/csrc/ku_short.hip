@@ -19,6 +19,7 @@
 // instead of 104 instructions in stage 2) ran 30.7 ms against 19.4 ms -- a bucket-header load instruction then covers
 // every second k-mer, only two lanes instead of four share a bucket line per instruction, and the number of line
 // requests, the scarce resource of the probe, doubles.
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -410,12 +411,21 @@ __device__ __forceinline__ uint32_t ks_g_insert_items(unsigned long long *g_key,
 // k-mer position, the slot is returned[kb[ticket >> 5] + (ticket & 31)] (KuRouteIn).  Everything behind the probe -- hit
 // counts, resolve_tree, call, n_reads (DO_COUNTS), the per-k-mer taxids in place of the tickets or as runs -- is the
 // code below, unchanged: the gather of the slots and the resolve are one pass over the per-k-mer array.
+// The instances whose waves can claim their reads from a counter of the launch (`chunk` below): the claim's state -- the chunk, the
+// cell, two read indices, the pending add -- fits them as they are.  The accounting instances with two k-mers per lane that write
+// runs or take reads in windows sit at their 80 registers already: with the claim compiled in they spill (16 B more scratch each,
+// scripts/kernel_resources.py), so they keep the static stride, and so do the ROUTE instances.  The host asks the same function
+// before it sizes a grid (ks_chunk).
+__host__ __device__ constexpr bool ks_claim_instance(int items, bool counts, bool win, int out, bool route) {
+  return !route && (items == 3 || !counts || (!win && out == 0));
+}
 template <int ITEMS, bool DO_COUNTS, int KK, int MM, bool WIN, int OUT, bool ROUTE = false>
 __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_short_kernel(
     KuDbDev db, KuTaxDev tax, KuCountsDev cnt, const uint8_t *__restrict__ seqs, uint64_t n_bytes,
     const uint64_t *__restrict__ seq_off, const uint32_t *__restrict__ seq_len, uint64_t n_reads,
     uint32_t *__restrict__ calls, uint32_t *__restrict__ taxa, uint32_t ablate, uint32_t floor_every,
-    uint32_t *__restrict__ spill, uint32_t spill_cap, KuRunsOut ro, KuSparseFast sf, KuRouteIn rin) {
+    uint32_t *__restrict__ spill, uint32_t spill_cap, KuRunsOut ro, KuSparseFast sf, KuRouteIn rin, uint32_t claim_chunk,
+    uint32_t *__restrict__ cell) {
   // KS_ABL(bit): measurement knob, compiled in only with -DKU_ABLATION (then env KU_ABLATE selects the bits; the
   // production build has no trace of it -- the flag checks cost scalar registers and branches in the read loop):
   // 1 skip probe, 2 skip HLL, 4 skip n_kmers, 8 skip taxa store,
@@ -454,6 +464,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
   ks_wave_sync();
 
   const uint32_t n_waves = gridDim.x * KS_WAVES;  // (a grid is a few blocks per CU)
+  const uint32_t wave_id = blockIdx.x * KS_WAVES + wv;
   // WIN: this wave's region of the spill workspace (keys, then values), wiped on first use
   uint32_t *g_key = WIN ? spill + ((uint64_t)blockIdx.x * KS_WAVES + wv) * 2ull * spill_cap : nullptr;
   uint32_t *g_cnt = WIN ? g_key + spill_cap : nullptr;
@@ -508,12 +519,33 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
   // the direct way: request all, raise.
   uint32_t hq_fill = 0;  // entries in the queue (wave-uniform)
   uint2 *hq = reinterpret_cast<uint2 *>(sw.hq);
+  // Which reads a wave takes.  chunk = 0: wave w takes reads w, w + n_waves, ... -- a fixed share, whatever the wave's CU, XCD
+  // and memory channels make of it, and the launch ends on the slowest wave's.  chunk > 0: the waves CLAIM their reads, `chunk`
+  // consecutive ones at a time, from one counter of the launch (cell[0]; KuClaimCells, ku_internal.h) and keep going until the
+  // batch is empty: a grid of as many waves as the device holds at once, none of them set up or flushed for a second round, and
+  // a wave that gets cheap reads simply takes more of them.  Wave w's first chunk is [w * chunk, (w + 1) * chunk) without an
+  // add; the counter hands out what lies behind the first chunks, n_waves * chunk + (its value before the add).  A claim at or
+  // behind n_reads ends the read loop by its own condition; nothing waits for another wave or for the host.  Which wave
+  // classifies a read enters no result: registers are maxima, counters sums, floors only filter, run chunks are claimed anyway.
+  // The add is a round trip to one L2 line, so it is requested at least one whole read before its value is looked at, and the value
+  // stays in lane 0 of `claim_v` until then: at the top of a chunk's LAST read the wave takes the base of the next chunk out of it
+  // -- requested at the top of the chunk before's last read, or in front of the loop -- and requests the one after that.  r_next,
+  // what the two paths that look one read ahead take (length / offset here, text_request), is r + 1 inside a chunk and that base
+  // on its last read.  A wave leaves the loop with one claim it never looks at: it was made after one that was at or behind
+  // n_reads already, so it holds no read.  (Read indices of a claiming launch are 32-bit: ks_chunk.)
+  // Only the instances of ks_claim_instance() have the code: in the others chunk is the constant 0.
+  const uint32_t chunk = ks_claim_instance(ITEMS, DO_COUNTS, WIN, OUT, ROUTE) ? claim_chunk : 0u;
+  uint64_t r = chunk ? (uint64_t)(wave_id * chunk) : (uint64_t)wave_id;
+  uint32_t r_next = 0;        // chunk > 0: the read after r
+  uint32_t claim_left = chunk;  // reads of the current chunk not started yet
+  uint32_t claim_v = 0;       // lane 0: the counter before this wave's newest add
+  auto claim_request = [&]() {
+    if (lane == 0) claim_v = atomicAdd(cell, chunk);
+  };
+  if (chunk) claim_request();
   uint32_t len_n = 0;
   uint64_t off_n = 0;
-  {
-    const uint64_t r0 = (uint64_t)blockIdx.x * KS_WAVES + wv;
-    if (ks_less64(r0, n_reads)) { len_n = seq_len[r0]; off_n = seq_off[r0]; }
-  }
+  if (ks_less64(r, n_reads)) { len_n = seq_len[r]; off_n = seq_off[r]; }
   // The read's text, one read ahead (one-pass instances whose stage 1 is one round of lanes).  A wave's vector loads complete in issue
   // order and a wait leaves the youngest ones outstanding: the next read's two dwords per lane, requested BEHIND the last loads this
   // read waits for (the single taxon's code and floors; the several-taxa read's gathers), cost none of this read's waits anything and
@@ -530,6 +562,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
   uint32_t tx0 = 0, tx1 = 0;
 #ifdef KU_ABLATION
   uint32_t tf0 = 0, tf1 = 0;  // (bit 2048: the dwords of the wave's first read)
+  bool tf_have = false;
 #endif
   // `first`: the request in front of the loop, for the wave's first read (measurement bit 2048 leaves that one alone and sends
   // every later one to the dummy address)
@@ -543,12 +576,21 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
     tx1 = tq[1];
   };
   if (AHEAD) text_request(true);
-  for (uint64_t r = (uint64_t)blockIdx.x * KS_WAVES + wv; ks_less64(r, n_reads); r += n_waves) {
+  for (; ks_less64(r, n_reads); r = chunk ? (uint64_t)r_next : r + n_waves) {
     // length and offset were requested one read ahead (two scalar loads off the chain of dependent round trips)
     const uint32_t rlen = len_n;
     const uint64_t roff = off_n;
     {
-      const uint64_t rn = r + n_waves;
+      uint64_t rn = r + n_waves;
+      if (chunk) {
+        r_next = (uint32_t)r + 1u;
+        if (--claim_left == 0) {  // the chunk's last read
+          r_next = n_waves * chunk + (uint32_t)__builtin_amdgcn_readfirstlane((int)claim_v);
+          claim_request();
+          claim_left = chunk;
+        }
+        rn = r_next;
+      }
       const bool more = ks_less64(rn, n_reads);
       len_n = more ? seq_len[rn] : 0u;
       off_n = more ? seq_off[rn] : 0ull;
@@ -623,7 +665,7 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
           uint32_t d0 = tx0, d1 = tx1;  // (AHEAD: requested inside the read before, by this very test)
 #ifdef KU_ABLATION
           if (AHEAD && KS_ABL(2048u)) {
-            if (ks_less64(r, n_waves)) { tf0 = d0; tf1 = d1; }
+            if (!tf_have) { tf0 = d0; tf1 = d1; tf_have = true; }
             else { d0 = tf0; d1 = tf1; }
           }
 #endif
@@ -1256,6 +1298,19 @@ __global__ __launch_bounds__(64 * KS_WAVES, KS_OCC(ITEMS)) void ku_classify_shor
   }
 #endif
   if (OUT == 2 && lane == 0 && sp_fresh) atomicAdd(sf.g_count, (unsigned long long)sp_fresh);
+  if (chunk) {
+    // The cell goes back to {0, 0} for the next launch of its stream.  Every wave of the grid comes here (no wave leaves the function
+    // early), with all its adds to cell[0] done -- the fence waits for the one it never looked at -- before it counts itself in
+    // cell[1]; the wave that counts last sets both words back, in plain stores behind a fence of its own.  (Counted by wave, not by
+    // block behind the barrier above: the instances without accounting have no barrier.)
+    __threadfence();
+    uint32_t through = 0;
+    if (lane == 0) through = atomicAdd(cell + 1, 1u);
+    if ((uint32_t)__builtin_amdgcn_readfirstlane((int)through) == n_waves - 1u) {
+      __threadfence();
+      if (lane == 0) { cell[0] = 0; cell[1] = 0; }
+    }
+  }
 }
 
 // k-mers per read the fused kernel can take (0 = not eligible): in one pass / in windows
@@ -1268,13 +1323,38 @@ uint32_t ku_short_max_kmers_windowed(const KuDbDev &db) {
   return ku_short_max_kmers(db) ? 65535u : 0u;  // 16-bit hit counts and scores per read
 }
 
-static unsigned ks_grid(uint64_t n_reads, int items, int n_cu) {
+// Reads a wave claims at a time (the kernel's comment on `chunk`); 0: the static stride.  A function of the launch's shape, its
+// instance and the environment alone: the grid, the run array's capacity and the windowed instance's workspace all follow from it
+// (ks_grid).  claims: ks_claim_instance() of the instance the launch selects.
+//   KU_SHORT_CLAIM=<n>         measurement knob, wins over the rest: 0 static, n that chunk
+//   KU_SHORT_BLOCKS_PER_CU     static: the knob says which reads meet on a wave, and tests rely on that
+//   else chunks of KS_CLAIM_CHUNK reads, when the launch has KS_CLAIM_MIN_PER_WAVE reads per resident wave; smaller launches stay static.
+// Both figures are the counter's, not the waves': every add of the launch goes to one address that all eight XCDs share, and
+// such adds are served one at a time, about 12 ns each.  The headline launch (10 M reads of 150 bases, 6144 waves, 15 ms) takes
+// 58.2 ms in chunks of 2, 30.3 in chunks of 4, 16.7 in chunks of 8 -- the adds alone -- and 14.96 / 14.99 in chunks of 16 / 32,
+// 15.2 / 15.3 in chunks of 48 / 64, against 16.4 static.  And the waves of a launch start together, so their first claims queue
+// up behind each other: launches of 1 M / 2 M / 3.3 M / 5 M / 10 M reads without accounting cost 17.4 / 15.5 / 14.7 / 14.2 / 13.7 ms
+// per 10 M reads in chunks of 16 (32: the same) against 14.8 / 14.6 / 14.6 / 14.6 / 14.5 static (profiles/claim_ab.log).  So the
+// claim pays from about 5 M reads per launch on, and a launch of the `classify` executable's size, 18 reads per wave, has
+// nothing to claim: a chunk the counter can serve is most of a wave's share.
+#define KS_CLAIM_CHUNK 32u
+#define KS_CLAIM_MIN_PER_WAVE 768ull
+static uint32_t ks_chunk(uint64_t n_reads, int items, int n_cu, bool claims) {
+  if (!claims || n_reads >= (1ull << 31)) return 0;  // (the counter and its overshoot are 32-bit)
+  if (const char *e = getenv("KU_SHORT_CLAIM")) return (uint32_t)std::min(std::max(atoi(e), 0), 4096);
+  if (getenv("KU_SHORT_BLOCKS_PER_CU")) return 0;
+  const uint64_t n_waves = (uint64_t)n_cu * KS_OCC(items) * KS_WAVES;
+  return n_reads < KS_CLAIM_MIN_PER_WAVE * n_waves ? 0u : KS_CLAIM_CHUNK;
+}
+static unsigned ks_grid(uint64_t n_reads, int items, int n_cu, bool claims) {
   // persistent grid: two rounds of the blocks a CU holds at once (KS_OCC blocks of KS_WAVES = 4 waves per CU) -- one round for the
   // launches of the `classify` executable's size, where a second round's waves would start up (LDS tables, first chunk) and flush
   // their counters for a handful of reads each (scripts/launch_shape_probe.py, launches of 120 k reads: 30.3 -> 24.9 ms per 10 M reads
-  // on one stream; from 1 M reads per launch on two rounds are the better: 19.95 against 20.32)
+  // on one stream; from 1 M reads per launch on two rounds are the better: 19.95 against 20.32) -- and ONE round whenever the waves
+  // claim their reads (ks_chunk): nothing is left for a second round's waves to do
   const char *oe = getenv("KU_SHORT_BLOCKS_PER_CU");
-  const uint64_t per_cu = oe ? (uint64_t)atoi(oe) : (n_reads < 500000 ? 1ull : 2ull) * KS_OCC(items);
+  const bool one_round = n_reads < 500000 || ks_chunk(n_reads, items, n_cu, claims) != 0;
+  const uint64_t per_cu = oe ? (uint64_t)atoi(oe) : (one_round ? 1ull : 2ull) * KS_OCC(items);
   const uint64_t want = (n_reads + KS_WAVES - 1) / KS_WAVES, cap = (uint64_t)n_cu * per_cu;
   return (unsigned)(want < cap ? want : cap);
 }
@@ -1288,18 +1368,20 @@ static uint32_t ks_spill_cap(uint32_t max_kmers, uint32_t n_slots) {
 // workspace of the windowed variant (0 when the reads fit one pass)
 uint64_t ku_short_workspace_bytes(uint32_t max_kmers, uint32_t n_slots, uint64_t n_reads, int n_cu) {
   if (max_kmers <= ks_one_pass_max()) return 0;
-  return (uint64_t)ks_grid(n_reads, 2, n_cu) * KS_WAVES * 2ull * ks_spill_cap(max_kmers, n_slots) * 4ull;
+  // (the larger of the two grids a windowed launch of this many reads can have: with and without the claim)
+  return (uint64_t)std::max(ks_grid(n_reads, 2, n_cu, false), ks_grid(n_reads, 2, n_cu, true)) * KS_WAVES * 2ull * ks_spill_cap(max_kmers, n_slots) * 4ull;
 }
 
-uint64_t ku_short_grid_waves(uint64_t n_reads, uint32_t max_kmers, int n_cu) {
+uint64_t ku_short_grid_waves(uint64_t n_reads, uint32_t max_kmers, int n_cu, bool counts) {
   const bool windowed = max_kmers > ks_one_pass_max();
-  return (uint64_t)ks_grid(n_reads, max_kmers <= 128 || windowed ? 2 : 3, n_cu) * KS_WAVES;
+  const int items = max_kmers <= 128 || windowed ? 2 : 3;
+  return (uint64_t)ks_grid(n_reads, items, n_cu, ks_claim_instance(items, counts, windowed, 1, false)) * KS_WAVES;  // (run output)
 }
 
 int ku_launch_classify_short(const KuDbDev &db, const KuTaxDev &tax, const KuCountsDev &cnt, const uint8_t *d_seqs,
                              uint64_t n_bytes, const uint64_t *d_seq_off, const uint32_t *d_seq_len, uint64_t n_reads,
                              uint32_t max_kmers, uint32_t flags, uint32_t *d_calls, uint32_t *d_taxa, uint32_t *d_hits,
-                             void *d_workspace, uint64_t workspace_bytes, int n_cu, hipStream_t stream,
+                             void *d_workspace, uint64_t workspace_bytes, int n_cu, hipStream_t stream, KuClaimCells &cells,
                              const KuRunsOut *runs_out, const KuSparseFast *sparse) {
   if (n_reads == 0) return KU_OK;
   const bool counts = !(flags & KU_F_NO_COUNTS);
@@ -1314,7 +1396,12 @@ int ku_launch_classify_short(const KuDbDev &db, const KuTaxDev &tax, const KuCou
   const uint32_t floor_every = fe ? (uint32_t)(atoi(fe) > 0 ? atoi(fe) : 0) : KS_FLOOR_EVERY;
   const bool windowed = max_kmers > ks_one_pass_max();
   const int items = max_kmers <= 128 || windowed ? 2 : 3;
-  const dim3 grid(ks_grid(n_reads, items, n_cu)), block(64 * KS_WAVES);
+  const int out = sparse ? 2 : (runs_out ? 1 : 0);
+  const bool claims = ks_claim_instance(items, counts, windowed, out, false);
+  const dim3 grid(ks_grid(n_reads, items, n_cu, claims)), block(64 * KS_WAVES);
+  const uint32_t chunk = ks_chunk(n_reads, items, n_cu, claims);
+  uint32_t *cell = chunk ? cells.cell(stream) : nullptr;
+  if (chunk && !cell) return KU_EINVAL;  // more streams than the ring has cells: no cell that is known to be idle
   uint32_t spill_cap = 0;
   if (windowed) {
     if (max_kmers > 65535u) return KU_EINVAL;
@@ -1323,11 +1410,10 @@ int ku_launch_classify_short(const KuDbDev &db, const KuTaxDev &tax, const KuCou
   }
   const KuRunsOut ro = runs_out ? *runs_out : KuRunsOut{};
   const KuSparseFast sf = sparse ? *sparse : KuSparseFast{};
-  const int out = sparse ? 2 : (runs_out ? 1 : 0);
 #define KS_LAUNCH(I, C, K, M, W, O)                                                                                          \
   hipLaunchKernelGGL((ku_classify_short_kernel<I, C, K, M, W, O>), grid, block, 0, stream, db, tax, cnt, d_seqs, n_bytes,    \
                      d_seq_off, d_seq_len, n_reads, d_calls, d_taxa, ablate, floor_every, (uint32_t *)d_workspace, spill_cap, ro, sf,   \
-                     KuRouteIn{})
+                     KuRouteIn{}, chunk, cell)
   // specialised geometries (accounting runs only): k = 31 with nt = 13 (MiniKraken-size databases) or 15 (standard)
   const int geo = !counts || db.k != 31 ? 0 : (db.nt == 13 ? 13 : (db.nt == 15 ? 15 : 0));
 #define KS_GEO(I, W, O)                                      \
@@ -1365,7 +1451,7 @@ int ku_launch_route_resolve(const KuDbDev &db, const KuTaxDev &tax, const KuCoun
   if (flags & (KU_F_KEEP_SLOTS | KU_F_QUICK)) return KU_EINVAL;
   if (d_hits && hipMemsetAsync(d_hits, 0, n_reads * 4, stream) != hipSuccess) return KU_EHIP;  // "Q:n" is quick mode only
   const bool counts = !(flags & KU_F_NO_COUNTS), windowed = max_kmers > 128;
-  const dim3 grid(ks_grid(n_reads, 2, n_cu)), block(64 * KS_WAVES);
+  const dim3 grid(ks_grid(n_reads, 2, n_cu, false)), block(64 * KS_WAVES);
   uint32_t spill_cap = 0;
   if (windowed) {
     spill_cap = ks_spill_cap(max_kmers, tax.n_slots);
@@ -1376,7 +1462,7 @@ int ku_launch_route_resolve(const KuDbDev &db, const KuTaxDev &tax, const KuCoun
 #define KS_RLAUNCH(C, W, O)                                                                                                     \
   hipLaunchKernelGGL((ku_classify_short_kernel<2, C, 0, 0, W, O, true>), grid, block, 0, stream, db, tax, cnt, (const uint8_t *)nullptr, \
                      (uint64_t)0, d_seq_off, d_seq_len, n_reads, d_calls, d_taxa, 0u, 0u, (uint32_t *)d_workspace, spill_cap, ro, \
-                     KuSparseFast{}, rin)
+                     KuSparseFast{}, rin, 0u, (uint32_t *)nullptr)
 #define KS_RSEL(W, O)                  \
   do {                                 \
     if (counts) KS_RLAUNCH(true, W, O); \
